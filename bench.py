@@ -11,7 +11,7 @@ gamma + PPM bytes (main.rs:104, ppm.rs:13-19) into the row-major payload.
 "Sample" = one path segment = one closest-hit query (raytrace.rs:14); the
 per-frame segment count is counted on the device in an untimed pass.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Without a torchrun environment, --gpus N > 1 starts the N ranks itself: torchrun
@@ -20,11 +20,17 @@ the line; its exit code is bench.py's.  Under torchrun, --gpus must equal
 WORLD_SIZE.  The line carries world_size_seen (dist.get_world_size()) and each
 rank's device (PCI id; distinct under nccl, or every rank exits non-zero).
 
-Rank 0 prints ONE JSON line.  Extras: "roofline" (the path kernel's f64 VALU
-issue roofline: PMC instruction mix of its launch over the chip's issue limit,
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps
+and reports the headline figure (value, ms_per_step, the HIP-event phases of the
+timed steps).  --dump-outputs DIR then writes what the last timed step computed
+(dump_outputs below).  Everything that takes runs of its own is behind --full:
+"roofline" (the path kernel's f64 VALU issue roofline: PMC instruction mix of its launch over the chip's issue limit,
 timed by HIP events; plus its measured HBM rate and the SURVEY §8d algorithmic
 byte rate) and "cpu_baseline" (the oracle, the C restatement of the reference, timed on
-a bounded row window of the same frame on the host cores; rank 0, N=1 only).
+a bounded row window of the same frame on the host cores; rank 0, N=1 only),
+the payload's device-to-host copy time ("phases_ms.d2h", "end_to_end_ms_per_step")
+and the frame digest ("image_sha256").  --no-pmc / --no-cpu-baseline drop one leg of
+a --full run.
 """
 import argparse
 import hashlib
@@ -420,6 +426,32 @@ def cpu_baseline(desc, params, target_s, runs=3):
     return out
 
 
+DUMP_BYTES = 30_000_000  # per array; two arrays stay under the 64 MB a dump may take
+DUMP_SEED = 0
+
+
+def dump_array(path, a, dtype):
+    """Write `a` as `dtype` to path; an array over DUMP_BYTES is written as a fixed,
+    seeded sample of its flattened elements (sorted indices, the same for every run
+    of the same shape)."""
+    a = np.asarray(a)
+    keep = DUMP_BYTES // np.dtype(dtype).itemsize
+    if a.size > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(path, np.ascontiguousarray(a, dtype=dtype))
+
+
+def dump_outputs(dirname, image, radiance):
+    """What a caller of the timed path receives from its last step, as .npy files:
+    image.npy     the PPM payload [H][W][3] (bytes 0..255, as float32);
+    radiance.npy  the gathered packed tiles [world][slots][256][3] of mean radiance
+                  (float64), the epilogue's input."""
+    os.makedirs(dirname, exist_ok=True)
+    dump_array(os.path.join(dirname, "image.npy"), image.cpu().numpy(), np.float32)
+    dump_array(os.path.join(dirname, "radiance.npy"), radiance.cpu().numpy(), np.float64)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -428,8 +460,14 @@ def main():
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--spp", type=int, default=None, help="override spp (not the headline config)")
     ap.add_argument("--cpu-seconds", type=float, default=18.0, help="CPU work per oracle build (split over 3 runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline=null)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the rocprofv3 --pmc roofline passes, the CPU "
+                         "baseline, the payload's D2H copy, the frame digest")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="with --full: skip the rocprofv3 --pmc child passes (roofline=null)")
     ap.add_argument("--as-rank0-of", type=int, default=0, help=argparse.SUPPRESS)  # PMC child: rank 0's share
     ap.add_argument("--tune", default="", help="experiments: force rt_tuning fields, e.g. compact=0,waves=4 "
                                                   "(the headline runs the library's own pick)")
@@ -453,8 +491,8 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.as_rank0_of:  # a PMC child is a standalone process, whatever its environment says
         world, rank, local = 1, 0, 0
-    pmc, pmc_ns = None, "not collected (--no-pmc)"
-    if rank == 0 and not args.no_pmc and not args.as_rank0_of:  # before this process touches the GPU
+    pmc, pmc_ns = None, "not collected (--no-pmc)" if args.full else "not collected (a --full run collects them)"
+    if rank == 0 and args.full and not args.no_pmc and not args.as_rank0_of:  # before this process touches the GPU
         pmc, pmc_ns = pmc_counters(args, world)
     ndev = torch.cuda.device_count()
     if world > 1 and args.dist_backend == "nccl" and world > ndev:
@@ -489,8 +527,10 @@ def main():
     per = scene.tiles_per_rank(params, part)
     stream = torch.cuda.current_stream(dev)
     sptr = stream.cuda_stream
-    tiles = torch.empty((per, 256, 3), dtype=torch.float64, device=dev)
-    gathered = torch.empty((world, per, 256, 3), dtype=torch.float64, device=dev) if rank == 0 else None
+    # a dump must not carry uninitialised slots (tile pixels past the frame's edge, spare tile slots)
+    alloc = torch.zeros if args.dump_outputs else torch.empty
+    tiles = alloc((per, 256, 3), dtype=torch.float64, device=dev)
+    gathered = alloc((world, per, 256, 3), dtype=torch.float64, device=dev) if rank == 0 else None
     # the epilogue writes the PPM payload (tonemap + gamma + bytes fused into the unpack)
     image = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if rank == 0 else None
 
@@ -508,6 +548,7 @@ def main():
     # HIP events on the stream the kernels run on, per timed step: [render, gather,
     # epilogue] boundaries (the gather and epilogue pair stay unrecorded in a PMC child)
     ev = []
+    last = {}  # the last step's gathered tiles (rank 0), for --dump-outputs
 
     def mark():
         e = torch.cuda.Event(enable_timing=True)
@@ -534,6 +575,7 @@ def main():
             marks.append(mark())
         if rank == 0:
             rt.unpack_tiles_bytes_async(params, world, src.data_ptr(), image.data_ptr(), sptr)
+            last["radiance"] = src
         if timed:
             marks.append(mark())
 
@@ -551,8 +593,10 @@ def main():
     elapsed = time.perf_counter() - t
     # the host copy of the frame's PPM payload (main.rs:74 writes it), outside the timed
     # region: SURVEY §8d's end-to-end figure = ms_per_step + this D2H (pinned host buffer)
+    if rank == 0 and part == world and args.dump_outputs:
+        dump_outputs(args.dump_outputs, image, last["radiance"].reshape(world, per, 256, 3))
     d2h_ms = None
-    if rank == 0 and part == world:
+    if rank == 0 and part == world and args.full:
         host_img = torch.empty(tuple(image.shape), dtype=torch.uint8, pin_memory=True)
         d2h = []
         for _ in range(3):
@@ -667,14 +711,16 @@ def main():
                           "d2h": d2h_ms},
             # kernel-only (roofline.kernel_ms), whole step on the device (ms_per_step:
             # render + gather + epilogue), and end to end with the payload's host copy
-            "end_to_end_ms_per_step": elapsed / args.steps * 1e3 + (d2h_ms or 0.0),
+            # (--full measures the copy; a plain run reports None)
+            "end_to_end_ms_per_step": elapsed / args.steps * 1e3 + d2h_ms if args.full else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(desc, params, args.cpu_seconds)
             cb = out["cpu_baseline"]["value"]
             out["speedup_vs_cpu"] = value / cb if cb else None
-        # the PPM payload of the last frame (outside the timed region): identical for any N
-        out["image_sha256"] = hashlib.sha256(image.cpu().numpy().tobytes()).hexdigest()
+        if args.full:
+            # the PPM payload of the last frame (outside the timed region): identical for any N
+            out["image_sha256"] = hashlib.sha256(image.cpu().numpy().tobytes()).hexdigest()
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

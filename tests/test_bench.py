@@ -139,3 +139,22 @@ def test_cpu_baseline_without_any_oracle_build(monkeypatch):
     assert out["value"] is None and out["value_build"] is None
     assert set(out["builds"]) == {"native", "portable"}
     assert all("no compiler" in v["error"] for v in out["builds"].values())
+
+
+def test_dump_array_samples_large_outputs(tmp_path):
+    """--dump-outputs: an array within the cap is written whole in the asked dtype; a larger
+    one as a fixed, seeded sample of its elements (the same indices on every run)."""
+    import numpy as np
+    b = _bench()
+    small = np.arange(24, dtype=np.uint8).reshape(2, 4, 3)
+    b.dump_array(str(tmp_path / "s.npy"), small, np.float32)
+    got = np.load(tmp_path / "s.npy")
+    assert got.dtype == np.float32 and got.shape == small.shape and np.array_equal(got, small)
+    n = b.DUMP_BYTES // 8 + 1000
+    big = np.arange(n, dtype=np.float64).reshape(-1, 8)
+    b.dump_array(str(tmp_path / "a.npy"), big, np.float64)
+    b.dump_array(str(tmp_path / "b.npy"), big.copy(), np.float64)
+    x, y = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    assert x.dtype == np.float64 and x.shape == (b.DUMP_BYTES // 8,) and x.nbytes <= b.DUMP_BYTES
+    assert np.array_equal(x, y) and (np.diff(x) > 0).all()  # the values are their own indices: sorted, distinct
+    assert 2 * b.DUMP_BYTES <= 64e6

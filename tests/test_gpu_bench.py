@@ -14,7 +14,8 @@ from conftest import REPO
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-BASE = ["--workload", "C1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+# --full: the digest and the PMC roofline are legs of a full run (a plain run times the steps only)
+BASE = ["--workload", "C1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
 ARGS = BASE + ["--no-pmc"]
 
 
@@ -63,3 +64,24 @@ def test_bench_gpus2_gloo_with_pmc_passes():
     r = b["roofline"]
     assert r["frac"] is not None and r["frac"] > 0, r
     assert r["hbm"]["frac"] > 0 and r["traffic"] > 0
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: no PMC children, no CPU
+    baseline, no digest.  --dump-outputs writes the last timed step's outputs: the PPM
+    payload and the packed radiance tiles it was made from."""
+    import numpy as np
+    d = tmp_path / "out"
+    r = _run(["--dump-outputs", str(d)], args=["--workload", "C1", "--steps", "2", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _line(r.stdout)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert "cpu_baseline" not in line and "image_sha256" not in line and line["roofline"]["frac"] is None
+    assert sorted(p.name for p in d.iterdir()) == ["image.npy", "radiance.npy"]
+    img, rad = np.load(d / "image.npy"), np.load(d / "radiance.npy")
+    assert img.dtype == np.float32 and img.shape == (256, 256, 3)
+    assert rad.dtype == np.float64 and rad.shape == (1, 256, 256, 3)  # 16x16 tiles of 256 pixels
+    assert img.nbytes + rad.nbytes <= 64e6
+    assert np.array_equal(img, np.round(img)) and img.min() >= 0 and img.max() <= 255 and img.max() > 0
+    assert np.isfinite(rad).all() and rad.min() >= 0 and rad.max() > 0

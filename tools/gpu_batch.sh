@@ -24,14 +24,14 @@ run() {  # run <name> <seconds> <cmd...>
 for s in $STEPS; do
   case $s in
     tests) run pytest_gpu 1000 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread || exit 1 ;;
-    bench) run bench_default 900 $B --gpus 1 --steps 20 --warmup 5 || exit 1 ;;
+    bench) run bench_default 900 $B --gpus 1 --steps 20 --warmup 5 --full || exit 1 ;;
     multi) run pytest_multi 600 python3 -u -m pytest tests/test_gpu_multi.py -m gpu -x -v --timeout 300 \
              --timeout-method thread || exit 1 ;;
     dist2) # the N=2 bench path (PMC children, tile shares, one gather, max-over-ranks) as a gloo rehearsal
       run bench_dist2 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --dist-backend gloo || exit 1 ;;
+        --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --dist-backend gloo --full || exit 1 ;;
     rehearse8)  # the driver's exact N=8 command, PMC passes on, all 8 gloo ranks on this one GPU
-      run bench_rehearsal_gloo8_pmc 900 $B --gpus 8 --dist-backend gloo || exit 1 ;;
+      run bench_rehearsal_gloo8_pmc 900 $B --gpus 8 --dist-backend gloo --full || exit 1 ;;
     wr2|wr3|wr5)  # where the writes come from: L2->fabric write requests by size, then the store
       # instruction mix (VMEM / FLAT incl. scratch) — $WR_LIB (default the product), $WR_SPP
       w=C${s#wr}
@@ -52,10 +52,10 @@ for s in $STEPS; do
         --no-cpu-baseline --no-pmc --spp ${HIT_SPP:-16} --tune "$TUNE" || exit 1 ;;
     tc3|tc5)  # the full-frame bench of C3 / C5 with --tune $TUNE (a kernel form the host does not pick yet)
       w=C${s#tc}
-      run bench_${w}_$(echo "$TUNE" | tr ',=' '__') 900 $B --workload $w --steps 2 --warmup 1 --tune "$TUNE" || exit 1 ;;
-    c2)    run bench_c2 600 $B --workload C2 --steps 3 --warmup 1 || exit 1 ;;
-    c3)    run bench_c3 600 $B --workload C3 --steps 3 --warmup 1 || exit 1 ;;
-    c5)    run bench_c5 900 $B --workload C5 --steps 2 --warmup 1 || exit 1 ;;
+      run bench_${w}_$(echo "$TUNE" | tr ',=' '__') 900 $B --workload $w --steps 2 --warmup 1 --full --tune "$TUNE" || exit 1 ;;
+    c2)    run bench_c2 600 $B --workload C2 --steps 3 --warmup 1 --full || exit 1 ;;
+    c3)    run bench_c3 600 $B --workload C3 --steps 3 --warmup 1 --full || exit 1 ;;
+    c5)    run bench_c5 900 $B --workload C5 --steps 2 --warmup 1 --full || exit 1 ;;
     prof2) run prof_c2 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c2" -o run \
              -- $B --workload C2 --steps 2 --warmup 1 --no-cpu-baseline --no-pmc || exit 1 ;;
     prof3) run prof_c3 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c3" -o run \
@@ -112,7 +112,7 @@ for s in $STEPS; do
     share2) run share_C2 600 python3 tools/share_scaling.py C2 256 1 8 || exit 1 ;;
     share4) run share_C4 900 python3 tools/share_scaling.py C4 1024 1 8 || exit 1 ;;
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    c4)    run bench_c4 900 $B --workload C4 --steps 2 --warmup 1 || exit 1 ;;
+    c4)    run bench_c4 900 $B --workload C4 --steps 2 --warmup 1 --full || exit 1 ;;
     prof4) run prof_c4 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c4" -o run \
              -- $B --workload C4 --steps 2 --warmup 1 --no-cpu-baseline --no-pmc || exit 1 ;;
     prof5) run prof_c5 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c5" -o run \
