@@ -111,11 +111,14 @@ class rt_tuning(C.Structure):
 TUNING_AUTO = dict(waves=0, resume=-1, kinds=0, suspend_lanes=0, leaf_lanes=0, chunk_spp=0, compact=-1, tail_split=0)
 RT_LAYOUT_COMPACT_TRIS = 0x1
 RT_LAYOUT_PAIR_NODES = 0x4
+RT_LAYOUT_DEVICE_BUILT = 0x8
+RT_BUILD_DEVICE = 0x1
 
 
 # every symbol include/rt_api.h declares (checked by tests/test_abi.py)
 EXPORTS = {
     "rt_scene_create": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_void_p)]),
+    "rt_scene_create_ex": (C.c_int, [C.POINTER(rt_scene_desc), C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_scene_destroy": (None, [C.c_void_p]),
     "rt_scene_get_info": (C.c_int, [C.c_void_p, C.POINTER(rt_scene_info)]),
     "rt_scene_checksum": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -152,6 +155,8 @@ EXPORTS = {
     "rt_probe_fp64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_bvh_build": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(C.c_uint32)]),
+    "rt_bvh_build_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_multi_create": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_int), C.c_uint32, C.c_uint32,
                                   C.POINTER(C.c_void_p)]),
     "rt_multi_render": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_void_p, C.c_void_p,
@@ -347,13 +352,16 @@ def load_gltf(path: str, width: int, height: int, spp: int):
 
 
 class Scene:
-    """Scene::new: BVHs built on the host, flattened arrays resident on the current HIP device."""
+    """Scene::new: BVHs built on the host (build="device": the triangle BVHs on the current
+    HIP device, the same trees), flattened arrays resident on the current HIP device."""
 
-    def __init__(self, desc: SceneDesc):
+    def __init__(self, desc: SceneDesc, build: str = "host"):
+        if build not in ("host", "device"):
+            raise ValueError(f"build must be 'host' or 'device', not {build!r}")
         self.desc = desc
         d, keep = desc.to_c()
         h = C.c_void_p()
-        _check(lib().rt_scene_create(C.byref(d), C.byref(h)))
+        _check(lib().rt_scene_create_ex(C.byref(d), RT_BUILD_DEVICE if build == "device" else 0, C.byref(h)))
         self._h = h
         del keep
 
@@ -617,6 +625,21 @@ def build_bvh(boxes: np.ndarray):
                               links.ctypes.data_as(C.c_void_p), bounds.ctypes.data_as(C.c_void_p),
                               order.ctypes.data_as(C.c_void_p), C.byref(depth)))
     return links, bounds, order, depth.value
+
+
+def build_bvh_device(boxes: np.ndarray, max_levels: int = 0):
+    """build_bvh on the current HIP device -> (links, bounds, order, depth, on_device); on_device is 0
+    when the host builder made the tree (rt_bvh_build_device).  max_levels 0: the library's cap."""
+    boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 6)
+    n = C.c_uint64(max(1, 2 * len(boxes)))  # a tree over n boxes has at most 2n - 1 nodes
+    depth, on_device = C.c_uint32(0), C.c_uint32(0)
+    links = np.zeros((n.value, 4), np.int64)
+    bounds = np.zeros((n.value, 6), np.float64)
+    order = np.zeros(len(boxes), np.uint64)
+    _check(lib().rt_bvh_build_device(boxes.ctypes.data_as(C.c_void_p), len(boxes), max_levels, C.byref(n),
+                                     links.ctypes.data_as(C.c_void_p), bounds.ctypes.data_as(C.c_void_p),
+                                     order.ctypes.data_as(C.c_void_p), C.byref(depth), C.byref(on_device)))
+    return links[:n.value].copy(), bounds[:n.value].copy(), order, depth.value, on_device.value
 
 
 def byte_thresholds() -> np.ndarray:

@@ -534,20 +534,29 @@ int rt_device_count(void) {
     return n;
 }
 
-int rt_scene_create(const rt_scene_desc* desc, rt_scene** out) {
+int rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out) {
     if (!desc || !out) return set_error(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
+    if (build_flags & ~RT_BUILD_DEVICE) return set_error(RT_ERR_INVALID, "unknown build flag");
     HostScene hs;
-    const int rc = rt::scene_build_host(*desc, hs);
+    const int rc = rt::scene_build_host(*desc, hs, build_flags);
     return rc ? rc : rt::scene_upload(hs, out, false);
 }
+int rt_scene_create(const rt_scene_desc* desc, rt_scene** out) { return rt_scene_create_ex(desc, 0, out); }
 
 }  // extern "C"
 
 namespace rt {
 
-int scene_build_host(const rt_scene_desc& desc, HostScene& hs) {
-    std::string err = build_scene(desc, hs);
+static int tri_build_device(const std::vector<Box3>& boxes, HostBvh& out, std::string& err) {
+    return build_bvh_device(boxes, 0, out, err);
+}
+
+int scene_build_host(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags) {
+    int ndev = 0;
+    if ((build_flags & RT_BUILD_DEVICE) && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0))
+        return set_error(RT_ERR_DEVICE, "no HIP device visible (RT_BUILD_DEVICE builds on one)");
+    std::string err = build_scene(desc, hs, (build_flags & RT_BUILD_DEVICE) ? tri_build_device : nullptr);
     if (!err.empty()) return set_error(RT_ERR_INVALID, err);
     for (int k = 0; k < 6; ++k)  // traversal stack words carry node indices in 30 bits (render.hip child_word)
         if (hs.bvh[k].nodes.size() >= (1u << 30)) return set_error(RT_ERR_INVALID, "BVH exceeds 2^30 nodes");
@@ -637,7 +646,7 @@ int scene_upload(const HostScene& hs, rt_scene** out, bool replica) {
     s->compact_bytes = hs.bvh[2].cnodes.size() * sizeof(DevNodeC) + hs.bvh[2].ctris.size() * sizeof(float);
     s->pair_bytes = (hs.bvh[2].pnodes.size() + hs.bvh[2].ctris.size()) * sizeof(float);
     s->info.layout_flags = (d.tris.cnodes ? RT_LAYOUT_COMPACT_TRIS : 0u) | (d.lq_boxes ? RT_LAYOUT_LQ_SKIP : 0u) |
-                           (d.tris.pnodes ? RT_LAYOUT_PAIR_NODES : 0u);
+                           (d.tris.pnodes ? RT_LAYOUT_PAIR_NODES : 0u) | (hs.device_built ? RT_LAYOUT_DEVICE_BUILT : 0u);
     s->info.build_ms = hs.build_ms;
     s->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = owner.release();
@@ -947,12 +956,21 @@ int rt_intersect_lights_rays(rt_scene* s, const double* rays, uint32_t n, double
     return light_query(s, rays, n, 0, out_impact, out_count);
 }
 
-int rt_bvh_build(const double* boxes, uint64_t n, uint64_t* n_nodes, int64_t* out_links, double* out_bounds,
-                 uint64_t* out_order, uint32_t* out_depth) {
+// rt_bvh_build and rt_bvh_build_device: on_device null = the host builder
+static int bvh_build_out(const double* boxes, uint64_t n, uint32_t max_levels, uint64_t* n_nodes, int64_t* out_links,
+                         double* out_bounds, uint64_t* out_order, uint32_t* out_depth, uint32_t* on_device) {
     if ((!boxes && n) || !n_nodes) return set_error(RT_ERR_INVALID, "boxes/n_nodes is NULL");
     std::vector<Box3> b(n);
     for (uint64_t i = 0; i < n; ++i) b[i] = Box3{load3(boxes + 6 * i), load3(boxes + 6 * i + 3)};
-    HostBvh h = build_bvh(b);
+    HostBvh h;
+    int made = kDeviceBuildFallback;
+    if (on_device) {
+        std::string err;
+        made = build_bvh_device(b, max_levels, h, err);
+        if (made == kDeviceBuildError) return set_error(RT_ERR_DEVICE, err);
+        *on_device = made == kDeviceBuildDone;
+    }
+    if (made != kDeviceBuildDone) h = build_bvh(b);
     if (out_links && *n_nodes < h.nodes.size()) return set_error(RT_ERR_INVALID, "output too small");
     *n_nodes = h.nodes.size();
     if (out_depth) *out_depth = h.depth;
@@ -965,6 +983,16 @@ int rt_bvh_build(const double* boxes, uint64_t n, uint64_t* n_nodes, int64_t* ou
     }
     if (out_order) for (uint64_t i = 0; i < n; ++i) out_order[i] = h.order[i];
     return RT_OK;
+}
+
+int rt_bvh_build(const double* boxes, uint64_t n, uint64_t* n_nodes, int64_t* out_links, double* out_bounds,
+                 uint64_t* out_order, uint32_t* out_depth) {
+    return bvh_build_out(boxes, n, 0, n_nodes, out_links, out_bounds, out_order, out_depth, nullptr);
+}
+int rt_bvh_build_device(const double* boxes, uint64_t n, uint32_t max_levels, uint64_t* n_nodes, int64_t* out_links,
+                        double* out_bounds, uint64_t* out_order, uint32_t* out_depth, uint32_t* on_device) {
+    if (!on_device) return set_error(RT_ERR_INVALID, "on_device is NULL");
+    return bvh_build_out(boxes, n, max_levels, n_nodes, out_links, out_bounds, out_order, out_depth, on_device);
 }
 
 // Diagnostic: device f64 sqrt (op 0), division (op 1), the split division

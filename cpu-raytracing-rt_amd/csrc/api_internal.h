@@ -18,7 +18,7 @@ struct HostScene;
 // rt_scene_create in two halves (api.cpp): the host build (six BVHs, flattened
 // records) and the upload of that build to the current HIP device, so a
 // multi-GPU frame (multi.cpp) builds once and uploads one replica per device.
-int scene_build_host(const rt_scene_desc& desc, HostScene& hs);
+int scene_build_host(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags = 0);  // RT_BUILD_*
 int scene_upload(const HostScene& hs, rt_scene** out, bool replica);
 // A scene's device arrays in allocation order (with their sizes): a replica built
 // from the same HostScene allocates the same sequence, so array k of the replica

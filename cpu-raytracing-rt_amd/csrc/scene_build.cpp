@@ -445,10 +445,16 @@ void build_compact(const HostBvh& h, const std::vector<TriItem>& items, HostBvhA
     build_pairs(out, n_int);
 }
 
-void build_tri_bvh(const std::vector<TriItem>& items, HostBvhArrays& out, bool compact = false) {
+std::string build_tri_bvh(const std::vector<TriItem>& items, HostBvhArrays& out, bool compact, TriBvhBuild tri_build,
+                          bool& device_built) {
     std::vector<Box3> boxes(items.size());
     for (size_t i = 0; i < items.size(); ++i) boxes[i] = items[i].box;
-    HostBvh h = build_bvh(boxes);
+    HostBvh h;
+    std::string err;
+    const int made = tri_build ? tri_build(boxes, h, err) : kDeviceBuildFallback;
+    if (made == kDeviceBuildError) return err;
+    if (made == kDeviceBuildDone) device_built = true;
+    else h = build_bvh(boxes);
     flatten(h, out);
     if (compact && !h.nodes.empty()) build_compact(h, items, out);
     out.n_prims = (uint32_t)items.size();
@@ -471,6 +477,7 @@ void build_tri_bvh(const std::vector<TriItem>& items, HostBvhArrays& out, bool c
         out.mat.push_back(items[i].mat);
         out.gid.push_back(items[i].gid);
     }
+    return "";
 }
 
 bool is_light(const rt_material& m) {  // scene.rs:225-227
@@ -522,7 +529,7 @@ HostBvh build_bvh(const std::vector<Box3>& boxes) {
     return h;
 }
 
-std::string build_scene(const rt_scene_desc& d, HostScene& out) {
+std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_build) {
     auto t0 = std::chrono::steady_clock::now();
     if (d.n_materials == 0 && (d.n_shapes > 0 || d.n_triangles > 0)) return "scene has primitives but no materials";
     if (d.n_shapes > 0 && !d.shapes) return "shapes is NULL";
@@ -618,10 +625,13 @@ std::string build_scene(const rt_scene_desc& d, HostScene& out) {
     for (auto& it : tris) if (is_light(d.materials[it.mat])) ltris.push_back(it);
     build_shape_bvh(boxes, out.bvh[0]);
     build_shape_bvh(ells, out.bvh[1]);
-    build_tri_bvh(tris, out.bvh[2], true);  // the scene's triangle BVH: compact layout when exact
+    // the scene's triangle BVH: compact layout when exact
+    std::string err = build_tri_bvh(tris, out.bvh[2], true, tri_build, out.device_built);
+    if (!err.empty()) return err;
     build_shape_bvh(lboxes, out.bvh[3]);
     build_shape_bvh(lells, out.bvh[4]);
-    build_tri_bvh(ltris, out.bvh[5]);
+    err = build_tri_bvh(ltris, out.bvh[5], false, tri_build, out.device_built);
+    if (!err.empty()) return err;
     out.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return "";
 }

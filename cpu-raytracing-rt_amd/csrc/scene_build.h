@@ -36,6 +36,21 @@ struct HostBvh {
 // BVH::new over primitive boxes given in list order (bvh.rs:12-17).
 HostBvh build_bvh(const std::vector<Box3>& boxes);
 
+// bvh_build.hip: build_bvh on the current HIP device, the same tree byte for byte.
+// kDeviceBuildFallback: nothing was built and the caller runs build_bvh — a coordinate
+// is NaN, infinite or above 2^480 in magnitude (up to there every SAH score of up to
+// 2^30 boxes is finite, whatever the boxes' signs, so no NaN reaches a comparison and
+// box_extend stays associative), the tree has more than max_levels levels, there are
+// no or more than 2^30 boxes, or the scratch (about 0.7 kB per box) does not fit.
+// kDeviceBuildError: a HIP call failed or no device is visible; err says which.
+enum { kDeviceBuildError = -1, kDeviceBuildFallback = 0, kDeviceBuildDone = 1 };
+// The default max_levels.  A level is a fixed number of launches over all boxes, so the
+// cap bounds what a degenerate one-primitive-per-level tree can cost; a full-sweep SAH
+// tree over n boxes in leaves of <= 4 has at least log2(n / 4) levels (22 at 10M) and
+// scenes with clustered geometry reach two to three times that, so 128 leaves a wide margin.
+constexpr uint32_t kDeviceBuildMaxLevels = 128;
+int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBvh& out, std::string& err);
+
 // Flattened scene ready for upload: every array is a host vector that maps
 // 1:1 onto a device allocation (see api.cpp).
 struct HostBvhArrays {
@@ -65,8 +80,13 @@ struct HostScene {
     std::vector<int32_t> plane_gid;
     HostBvhArrays bvh[6];   // boxes, ellipsoids, triangles, light boxes, light ellipsoids, light triangles
     double build_ms = 0.0;
+    bool device_built = false;  // a triangle BVH came from build_bvh_device
 };
+// tri_build: makes the two triangle BVHs and returns as build_bvh_device does (the host
+// builder runs on kDeviceBuildFallback); null: the host builder.  The small shape BVHs
+// are always the host's.
+using TriBvhBuild = int (*)(const std::vector<Box3>& boxes, HostBvh& out, std::string& err);
 // Returns empty string on success, else an error message.
-std::string build_scene(const rt_scene_desc& desc, HostScene& out);
+std::string build_scene(const rt_scene_desc& desc, HostScene& out, TriBvhBuild tri_build = nullptr);
 
 }  // namespace rt

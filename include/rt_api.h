@@ -166,6 +166,13 @@ typedef struct rt_parsed_scene rt_parsed_scene; /* opaque, host-side parse resul
 /* Replaces Scene::new + make_scenes (src/scene.rs:180-223) and BVH::new
    (src/bvh.rs:12-17); uploads the flattened scene to the CURRENT HIP device. */
 int  rt_scene_create(const rt_scene_desc* desc, rt_scene** out);
+/* rt_scene_create with build flags (0: exactly rt_scene_create).  RT_BUILD_DEVICE: the
+   triangle and light-triangle BVHs are built on the current HIP device, the same trees
+   byte for byte (rt_bvh_build_device; a BVH it cannot take is built on the host); the
+   small shape BVHs stay on the host.  build_ms then covers the device build and the
+   copy back. */
+#define RT_BUILD_DEVICE 0x1u
+int  rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
 
 typedef struct rt_scene_info {
@@ -175,7 +182,7 @@ typedef struct rt_scene_info {
     uint64_t n_light_triangles;
     uint64_t bvh_nodes[6];       /* boxes, ellipsoids, triangles, light boxes, light ellipsoids, light triangles */
     uint32_t bvh_depth[6];
-    double   build_ms;           /* host BVH build                                */
+    double   build_ms;           /* BVH build (host, or device with RT_BUILD_DEVICE) */
     double   upload_ms;          /* H2D copy                                      */
     uint64_t device_bytes;       /* the scene's arrays; the per-launch workspace (commit
                                     ring, split-tail row buffer <= 256 MB, chunk partials
@@ -200,6 +207,9 @@ typedef struct rt_scene_info {
    one line per two levels), which the resumable kernel reads when it is
    there (rt_tuning.compact auto or 2) */
 #define RT_LAYOUT_PAIR_NODES   0x4u
+/* RT_LAYOUT_DEVICE_BUILT: a triangle BVH of the scene was built on the device
+   (rt_scene_create_ex with RT_BUILD_DEVICE); the arrays are the host build's */
+#define RT_LAYOUT_DEVICE_BUILT 0x8u
 int rt_scene_get_info(const rt_scene* scene, rt_scene_info* out);
 /* Content hash of the scene's device arrays (BVHs, records, materials; not the
    per-launch workspace), computed on the scene's device.  Two handles built from the
@@ -386,6 +396,14 @@ int rt_intersect_lights_rays(rt_scene* scene, const double* rays, uint32_t n,
    [n_nodes][6], out_order [n] = list index of the i-th primitive in BVH order. */
 int rt_bvh_build(const double* boxes, uint64_t n, uint64_t* n_nodes, int64_t* out_links,
                  double* out_bounds, uint64_t* out_order, uint32_t* out_depth);
+/* rt_bvh_build on the current HIP device: the same outputs, byte for byte (a tree has
+   at most 2n - 1 nodes, so buffers of that size need no sizing call).  max_levels 0 =
+   the library's cap.  *on_device = 1 when the device builder made the tree, 0 when the
+   host builder did: a coordinate that is NaN, infinite or above 2^480 in magnitude, a
+   tree deeper than max_levels, no or more than 2^30 boxes, or no memory for the scratch. */
+int rt_bvh_build_device(const double* boxes, uint64_t n, uint32_t max_levels,
+                        uint64_t* n_nodes, int64_t* out_links, double* out_bounds,
+                        uint64_t* out_order, uint32_t* out_depth, uint32_t* on_device);
 
 /* ======================= host input surface =============================== */
 /* Custom text format (src/scene_parser.rs:5-85, defaults scene.rs:167-191). */

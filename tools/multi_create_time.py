@@ -1,8 +1,11 @@
 """rt_multi_create of a bench workload's scene with N replicas (one GPU: a device listed N
 times, RT_MULTI_PEER): the host build once, devices[0] from the host, the replicas filled
 device to device from devices[0]; prints each replica's upload_ms beside a plain
-rt_scene_create (what one replica's own host upload costs).
-    python tools/multi_create_time.py [WORKLOAD] [N]"""
+rt_scene_create (what one replica's own host upload costs).  --build device builds that
+plain scene's triangle BVHs on the device (rt_scene_create_ex, RT_BUILD_DEVICE) and prints a
+second device-built scene's times too (the first one loads the builder's code object);
+rt_multi_create always builds on the host.
+    python tools/multi_create_time.py [WORKLOAD] [N] [--build host|device]"""
 import os
 import sys
 import time
@@ -15,17 +18,25 @@ import bench  # noqa: E402
 from conftest import load_package  # noqa: E402
 
 rt = load_package()
+build = "host"
+if "--build" in sys.argv:
+    k = sys.argv.index("--build")
+    build = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
 wl = sys.argv[1] if len(sys.argv) > 1 else "C5"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 scene_file, W, H, spp, _ = bench.WORKLOADS[wl]
 desc, params = bench.load_workload(rt, scene_file, W, H, spp)
-t = time.perf_counter()
-s = rt.Scene(desc)
-one = time.perf_counter() - t
-i0 = s.info()
-print(f"{wl}: rt_scene_create {one * 1e3:.0f} ms (build {i0['build_ms']:.0f} ms, host upload {i0['upload_ms']:.1f} ms, "
-      f"{i0['device_bytes'] / 1e9:.3f} GB)", flush=True)
-del s
+for _ in range(2 if build == "device" else 1):
+    t = time.perf_counter()
+    s = rt.Scene(desc, build=build)
+    one = time.perf_counter() - t
+    i0 = s.info()
+    if build == "device":
+        assert i0["layout_flags"] & rt.RT_LAYOUT_DEVICE_BUILT
+    print(f"{wl}: rt_scene_create ({build} build) {one * 1e3:.0f} ms (build {i0['build_ms']:.0f} ms, host upload {i0['upload_ms']:.1f} ms, "
+          f"{i0['device_bytes'] / 1e9:.3f} GB)", flush=True)
+    del s
 t = time.perf_counter()
 m = rt.MultiScene(desc, [0] * n, peer=True)
 tot = time.perf_counter() - t
