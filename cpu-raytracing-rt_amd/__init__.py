@@ -112,7 +112,9 @@ TUNING_AUTO = dict(waves=0, resume=-1, kinds=0, suspend_lanes=0, leaf_lanes=0, c
 RT_LAYOUT_COMPACT_TRIS = 0x1
 RT_LAYOUT_PAIR_NODES = 0x4
 RT_LAYOUT_DEVICE_BUILT = 0x8
+RT_LAYOUT_DEVICE_RECORDS = 0x10
 RT_BUILD_DEVICE = 0x1
+RT_BUILD_DEVICE_RECORDS = 0x2
 
 
 # every symbol include/rt_api.h declares (checked by tests/test_abi.py)
@@ -353,15 +355,21 @@ def load_gltf(path: str, width: int, height: int, spp: int):
 
 class Scene:
     """Scene::new: BVHs built on the host (build="device": the triangle BVHs on the current
-    HIP device, the same trees), flattened arrays resident on the current HIP device."""
+    HIP device, the same trees; records="device": their arrays written there too, not
+    uploaded), flattened arrays resident on the current HIP device."""
 
-    def __init__(self, desc: SceneDesc, build: str = "host"):
+    def __init__(self, desc: SceneDesc, build: str = "host", records: str = "host"):
         if build not in ("host", "device"):
             raise ValueError(f"build must be 'host' or 'device', not {build!r}")
+        if records not in ("host", "device"):
+            raise ValueError(f"records must be 'host' or 'device', not {records!r}")
+        if records == "device" and build != "device":
+            raise ValueError("records='device' needs build='device'")
         self.desc = desc
         d, keep = desc.to_c()
         h = C.c_void_p()
-        _check(lib().rt_scene_create_ex(C.byref(d), RT_BUILD_DEVICE if build == "device" else 0, C.byref(h)))
+        flags = (RT_BUILD_DEVICE if build == "device" else 0) | (RT_BUILD_DEVICE_RECORDS if records == "device" else 0)
+        _check(lib().rt_scene_create_ex(C.byref(d), flags, C.byref(h)))
         self._h = h
         del keep
 

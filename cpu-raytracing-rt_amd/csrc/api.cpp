@@ -98,10 +98,27 @@ int upload(rt_scene* s, const std::vector<T>& v, const T** out) {
     return RT_OK;
 }
 
+// Array k of a BVH: uploaded from its host vector, or, where bvh_emit.hip already wrote it
+// on the device (h.dev.on), adopted as it is — the same entry in allocs / alloc_bytes /
+// device_bytes as the upload would make, so the checksum and replicas see one sequence.
+template <class T>
+int upload(rt_scene* s, const HostBvhArrays& h, int k, const std::vector<T>& v, const T** out) {
+    if (!h.dev.on) return upload(s, v, out);
+    *out = nullptr;
+    if (!h.dev.ptr[k]) return RT_OK;
+    if (g_replica) return set_error(RT_ERR_INVALID, "a replica cannot adopt device-emitted arrays");
+    s->allocs.push_back(h.dev.ptr[k]);  // from here on the scene frees it
+    s->alloc_bytes.push_back(h.dev.count[k] * sizeof(T));
+    s->info.device_bytes += h.dev.count[k] * sizeof(T);
+    *out = (const T*)h.dev.ptr[k];
+    h.dev.ptr[k] = nullptr;
+    return RT_OK;
+}
+
 int upload_bvh(rt_scene* s, const HostBvhArrays& h, DevBvh& d) {
     int rc;
     std::memset(&d, 0, sizeof(d));
-    if ((rc = upload(s, h.nodes, &d.nodes))) return rc;
+    if ((rc = upload(s, h, kResNodes, h.nodes, &d.nodes))) return rc;
     store3(d.root_min, h.root.min);
     store3(d.root_max, h.root.max);
     d.n_prims = h.n_prims;
@@ -109,14 +126,14 @@ int upload_bvh(rt_scene* s, const HostBvhArrays& h, DevBvh& d) {
     d.fast = h.fast ? 1u : 0u;
     d.tri_q = h.tri_q ? 1u : 0u;
     if ((rc = upload(s, h.shapes, &d.shapes))) return rc;
-    if ((rc = upload(s, h.tris, &d.tris))) return rc;
-    if ((rc = upload(s, h.tri_cold, &d.tri_cold))) return rc;
-    if ((rc = upload(s, h.tri_inv_area, &d.tri_inv_area))) return rc;
-    if ((rc = upload(s, h.mat, &d.mat))) return rc;
-    if ((rc = upload(s, h.gid, &d.gid))) return rc;
-    if ((rc = upload(s, h.cnodes, &d.cnodes))) return rc;
-    if ((rc = upload(s, h.ctris, &d.ctris))) return rc;
-    if ((rc = upload(s, h.pnodes, &d.pnodes))) return rc;
+    if ((rc = upload(s, h, kResTris, h.tris, &d.tris))) return rc;
+    if ((rc = upload(s, h, kResCold, h.tri_cold, &d.tri_cold))) return rc;
+    if ((rc = upload(s, h, kResInvArea, h.tri_inv_area, &d.tri_inv_area))) return rc;
+    if ((rc = upload(s, h, kResMat, h.mat, &d.mat))) return rc;
+    if ((rc = upload(s, h, kResGid, h.gid, &d.gid))) return rc;
+    if ((rc = upload(s, h, kResCnodes, h.cnodes, &d.cnodes))) return rc;
+    if ((rc = upload(s, h, kResCtris, h.ctris, &d.ctris))) return rc;
+    if ((rc = upload(s, h, kResPnodes, h.pnodes, &d.pnodes))) return rc;
     return RT_OK;
 }
 
@@ -445,7 +462,7 @@ int copy_stats(rt_scene* s, rt_stats* out) {
 // light copies (scene.rs:209-213) byte-identical to the selected scene records.
 uint32_t slt_mask(const HostScene& hs) {
     const auto &B = hs.bvh[0], &L = hs.bvh[3];
-    if (L.shapes.empty() || !hs.bvh[4].shapes.empty() || !hs.bvh[5].tris.empty()) return 0;
+    if (L.shapes.empty() || !hs.bvh[4].shapes.empty() || hs.bvh[5].n_prims) return 0;
     if (B.depth != 1 || L.depth != 1 || B.shapes.size() > 32) return 0;
     uint32_t mask = 0;
     size_t j = 0;
@@ -467,7 +484,7 @@ uint32_t slt_mask(const HostScene& hs) {
 // and M is well conditioned (n within 10% of 1, the inverse checked).
 uint32_t lq_boxes(const HostScene& hs, double (*out)[6]) {
     const auto& L = hs.bvh[3].shapes;
-    if (L.empty() || L.size() > kLqBoxes || !hs.bvh[4].shapes.empty() || !hs.bvh[5].tris.empty()) return 0;
+    if (L.empty() || L.size() > kLqBoxes || !hs.bvh[4].shapes.empty() || hs.bvh[5].n_prims) return 0;
     for (size_t i = 0; i < L.size(); ++i) {
         const DevShape& b = L[i];
         const double pb = b.aux[0];
@@ -537,7 +554,9 @@ int rt_device_count(void) {
 int rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out) {
     if (!desc || !out) return set_error(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
-    if (build_flags & ~RT_BUILD_DEVICE) return set_error(RT_ERR_INVALID, "unknown build flag");
+    if (build_flags & ~(RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS)) return set_error(RT_ERR_INVALID, "unknown build flag");
+    if ((build_flags & RT_BUILD_DEVICE_RECORDS) && !(build_flags & RT_BUILD_DEVICE))
+        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_RECORDS needs RT_BUILD_DEVICE (the records come from the device's tree)");
     HostScene hs;
     const int rc = rt::scene_build_host(*desc, hs, build_flags);
     return rc ? rc : rt::scene_upload(hs, out, false);
@@ -551,15 +570,19 @@ namespace rt {
 static int tri_build_device(const std::vector<Box3>& boxes, HostBvh& out, std::string& err) {
     return build_bvh_device(boxes, 0, out, err);
 }
+static int tri_emit_device(const std::vector<TriItem>& items, bool compact, HostBvhArrays& out, std::string& err) {
+    return emit_tri_bvh_device(items, compact, 0, out, err);
+}
 
 int scene_build_host(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags) {
     int ndev = 0;
     if ((build_flags & RT_BUILD_DEVICE) && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0))
         return set_error(RT_ERR_DEVICE, "no HIP device visible (RT_BUILD_DEVICE builds on one)");
-    std::string err = build_scene(desc, hs, (build_flags & RT_BUILD_DEVICE) ? tri_build_device : nullptr);
+    std::string err = build_scene(desc, hs, (build_flags & RT_BUILD_DEVICE) ? tri_build_device : nullptr,
+                                  (build_flags & RT_BUILD_DEVICE_RECORDS) ? tri_emit_device : nullptr);
     if (!err.empty()) return set_error(RT_ERR_INVALID, err);
     for (int k = 0; k < 6; ++k)  // traversal stack words carry node indices in 30 bits (render.hip child_word)
-        if (hs.bvh[k].nodes.size() >= (1u << 30)) return set_error(RT_ERR_INVALID, "BVH exceeds 2^30 nodes");
+        if (hs.bvh[k].n_nodes() >= (1u << 30)) return set_error(RT_ERR_INVALID, "BVH exceeds 2^30 nodes");
     return RT_OK;
 }
 
@@ -627,7 +650,7 @@ int scene_upload(const HostScene& hs, rt_scene** out, bool replica) {
     const DevBvh* all[6] = {&d.boxes, &d.ells, &d.tris, &d.lboxes, &d.lells, &d.ltris};
     for (int k = 0; k < 6; ++k) {
         d.max_depth = std::max(d.max_depth, all[k]->depth);
-        s->info.bvh_nodes[k] = hs.bvh[k].nodes.size();
+        s->info.bvh_nodes[k] = hs.bvh[k].n_nodes();
         s->info.bvh_depth[k] = hs.bvh[k].depth;
     }
     HIP_TRY(hipMalloc(&s->d_scene, sizeof(DevScene)));
@@ -643,10 +666,13 @@ int scene_upload(const HostScene& hs, rt_scene** out, bool replica) {
     s->info.n_light_ellipsoids = d.lells.n_prims;
     s->info.n_light_triangles = d.ltris.n_prims;
     s->info.shared_light_mask = d.slt_mask;
-    s->compact_bytes = hs.bvh[2].cnodes.size() * sizeof(DevNodeC) + hs.bvh[2].ctris.size() * sizeof(float);
-    s->pair_bytes = (hs.bvh[2].pnodes.size() + hs.bvh[2].ctris.size()) * sizeof(float);
+    const HostBvhArrays& T = hs.bvh[2];
+    const uint64_t n_ctris = T.count(kResCtris, T.ctris.size());
+    s->compact_bytes = T.count(kResCnodes, T.cnodes.size()) * sizeof(DevNodeC) + n_ctris * sizeof(float);
+    s->pair_bytes = (T.count(kResPnodes, T.pnodes.size()) + n_ctris) * sizeof(float);
     s->info.layout_flags = (d.tris.cnodes ? RT_LAYOUT_COMPACT_TRIS : 0u) | (d.lq_boxes ? RT_LAYOUT_LQ_SKIP : 0u) |
-                           (d.tris.pnodes ? RT_LAYOUT_PAIR_NODES : 0u) | (hs.device_built ? RT_LAYOUT_DEVICE_BUILT : 0u);
+                           (d.tris.pnodes ? RT_LAYOUT_PAIR_NODES : 0u) | (hs.device_built ? RT_LAYOUT_DEVICE_BUILT : 0u) |
+                           (hs.device_records ? RT_LAYOUT_DEVICE_RECORDS : 0u);
     s->info.build_ms = hs.build_ms;
     s->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = owner.release();

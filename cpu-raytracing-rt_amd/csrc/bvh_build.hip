@@ -22,6 +22,7 @@
 #include <utility>
 #include <vector>
 
+#include "bvh_device.h"
 #include "scene_build.h"
 
 namespace rt {
@@ -495,8 +496,6 @@ __global__ void bb_preorder(uint32_t first, uint32_t end, Nodes nd) {
     nd.pre[l] = nd.pre[i] + 1;
     nd.pre[l + 1] = nd.pre[i] + 1 + nd.size[l];
 }
-struct OutNode { double box[6]; int64_t left, right; uint64_t start, end; };  // HostNode's bytes
-static_assert(sizeof(OutNode) == sizeof(HostNode) && sizeof(OutNode) == 80, "OutNode mirrors HostNode");
 __global__ void bb_emit(uint32_t n_nodes, Nodes nd, OutNode* out) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n_nodes) return;
@@ -516,27 +515,6 @@ __global__ void bb_order64(uint32_t n, const uint32_t* order, uint64_t* out) {
 }
 
 // ---------------------------------------------------------------- host ----
-struct Arena {  // per-call scratch: everything is freed before the call returns
-    std::vector<void*> ptrs;
-    bool oom = false;
-    hipError_t err = hipSuccess;
-    ~Arena() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T>
-    T* get(size_t count) {
-        void* p = nullptr;
-        if (oom || err != hipSuccess) return nullptr;
-        const hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
-        if (e == hipErrorOutOfMemory) { oom = true; (void)hipGetLastError(); return nullptr; }
-        if (e != hipSuccess) { err = e; return nullptr; }
-        ptrs.push_back(p);
-        return (T*)p;
-    }
-    void release(void* p) {
-        for (void*& q : ptrs) if (q == p && p) { (void)hipFree(p); q = nullptr; }
-    }
-    bool ok() const { return !oom && err == hipSuccess; }
-};
-
 inline uint32_t blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
 Segs alloc_segs(Arena& m, size_t n) {
@@ -555,30 +533,20 @@ Segs alloc_segs(Arena& m, size_t n) {
         if (e_ != hipSuccess) { err = hipGetErrorString(e_); return kDeviceBuildError; } \
     } while (0)
 
-int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBvh& out, std::string& err) {
-    const uint64_t n64 = boxes.size();
+int build_bvh_device_tree(Arena& m, const double* d_boxes, uint32_t n, uint32_t max_levels, DevTree& out,
+                          std::string& err) {
     if (max_levels == 0) max_levels = kDeviceBuildMaxLevels;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        err = "no HIP device visible (the device builder needs one)";
-        return kDeviceBuildError;
-    }
-    if (n64 == 0 || n64 > kMaxPrims) return kDeviceBuildFallback;
-    const uint32_t n = (uint32_t)n64;
     const size_t n3 = (size_t)n * 3;
-    Arena m;
+    const size_t mark = m.ptrs.size();
     const hipStream_t st = 0;
 
-    // boxes, keys, the presort
-    double* d_boxes = m.get<double>((size_t)n * 6);
+    // keys, the presort
     uint32_t* d_ctr = m.get<uint32_t>(4);  // next-level segments, nodes, ineligible flag
     uint32_t* ids[2] = {m.get<uint32_t>(n3), m.get<uint32_t>(n3)};
     unsigned long long* keys[2] = {m.get<unsigned long long>(n3), m.get<unsigned long long>(n3)};
     const uint32_t sblk = blocks(n, kSortTile);
     uint32_t* d_table = m.get<uint32_t>((size_t)3 * 256 * sblk);
     if (!m.ok()) { if (m.oom) return kDeviceBuildFallback; BB_TRY(m.err); }
-    static_assert(sizeof(Box3) == 48, "Box3 is six doubles");
-    BB_TRY(hipMemcpyAsync(d_boxes, boxes.data(), (size_t)n * 48, hipMemcpyHostToDevice, st));
     BB_TRY(hipMemsetAsync(d_ctr, 0, 4 * sizeof(uint32_t), st));
     bb_keys<<<blocks(n, kThreads), kThreads, 0, st>>>(d_boxes, n, keys[0], ids[0], d_ctr + 2);
     uint32_t bad = 0;
@@ -667,7 +635,6 @@ int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBv
     // numbering: sizes bottom-up, pre-order top-down, then the host's records
     m.release(sb[0]); m.release(sb[1]);
     OutNode* d_out = m.get<OutNode>(n_nodes);
-    uint64_t* d_order64 = m.get<uint64_t>(n);
     if (!m.ok()) { if (m.oom) return kDeviceBuildFallback; BB_TRY(m.err); }
     for (size_t l = level_start.size() - 1; l-- > 0;)
         bb_sizes<<<blocks(level_start[l + 1] - level_start[l], kThreads), kThreads, 0, st>>>(level_start[l],
@@ -676,12 +643,42 @@ int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBv
         bb_preorder<<<blocks(level_start[l + 1] - level_start[l], kThreads), kThreads, 0, st>>>(level_start[l],
                                                                                                 level_start[l + 1], nd);
     bb_emit<<<blocks(n_nodes, kThreads), kThreads, 0, st>>>(n_nodes, nd, d_out);
-    bb_order64<<<blocks(n, kThreads), kThreads, 0, st>>>(n, d_order, d_order64);
     BB_TRY(hipGetLastError());
-    out.nodes.resize(n_nodes);
-    out.order.resize(n);
+    BB_TRY(hipStreamSynchronize(st));
+    m.release_since(mark, d_out, d_order);
+    out.nodes = d_out;
+    out.order = d_order;
+    out.n_nodes = n_nodes;
     out.depth = depth;
-    BB_TRY(hipMemcpyAsync(out.nodes.data(), d_out, (size_t)n_nodes * sizeof(OutNode), hipMemcpyDeviceToHost, st));
+    return kDeviceBuildDone;
+}
+
+int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBvh& out, std::string& err) {
+    const uint64_t n64 = boxes.size();
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        err = "no HIP device visible (the device builder needs one)";
+        return kDeviceBuildError;
+    }
+    if (n64 == 0 || n64 > kMaxPrims) return kDeviceBuildFallback;
+    const uint32_t n = (uint32_t)n64;
+    Arena m;
+    const hipStream_t st = 0;
+    double* d_boxes = m.get<double>((size_t)n * 6);
+    if (!m.ok()) { if (m.oom) return kDeviceBuildFallback; BB_TRY(m.err); }
+    static_assert(sizeof(Box3) == 48, "Box3 is six doubles");
+    BB_TRY(hipMemcpyAsync(d_boxes, boxes.data(), (size_t)n * 48, hipMemcpyHostToDevice, st));
+    DevTree t;
+    const int made = build_bvh_device_tree(m, d_boxes, n, max_levels, t, err);
+    if (made != kDeviceBuildDone) return made;
+    uint64_t* d_order64 = m.get<uint64_t>(n);
+    if (!m.ok()) { if (m.oom) return kDeviceBuildFallback; BB_TRY(m.err); }
+    bb_order64<<<blocks(n, kThreads), kThreads, 0, st>>>(n, t.order, d_order64);
+    BB_TRY(hipGetLastError());
+    out.nodes.resize(t.n_nodes);
+    out.order.resize(n);
+    out.depth = t.depth;
+    BB_TRY(hipMemcpyAsync(out.nodes.data(), t.nodes, (size_t)t.n_nodes * sizeof(OutNode), hipMemcpyDeviceToHost, st));
     BB_TRY(hipMemcpyAsync(out.order.data(), d_order64, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     BB_TRY(hipStreamSynchronize(st));
     return kDeviceBuildDone;

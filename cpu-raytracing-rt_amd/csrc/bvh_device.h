@@ -1,0 +1,55 @@
+// bvh_device.h — what bvh_build.hip and bvh_emit.hip share: the builder's tree as it
+// stays in device memory, and the per-call scratch arena that owns it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "scene_build.h"
+
+namespace rt {
+
+struct OutNode { double box[6]; int64_t left, right; uint64_t start, end; };  // HostNode's bytes
+static_assert(sizeof(OutNode) == sizeof(HostNode) && sizeof(OutNode) == 80, "OutNode mirrors HostNode");
+
+struct Arena {  // per-call scratch: everything is freed before the call returns
+    std::vector<void*> ptrs;
+    bool oom = false;
+    hipError_t err = hipSuccess;
+    ~Arena() { for (void* p : ptrs) (void)hipFree(p); }
+    template <class T>
+    T* get(size_t count) {
+        void* p = nullptr;
+        if (oom || err != hipSuccess) return nullptr;
+        const hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
+        if (e == hipErrorOutOfMemory) { oom = true; (void)hipGetLastError(); return nullptr; }
+        if (e != hipSuccess) { err = e; return nullptr; }
+        ptrs.push_back(p);
+        return (T*)p;
+    }
+    void release(void* p) {
+        for (void*& q : ptrs) if (q == p && p) { (void)hipFree(p); q = nullptr; }
+    }
+    // everything taken since `mark` (ptrs.size() then) except the two kept
+    void release_since(size_t mark, const void* keep0, const void* keep1) {
+        for (size_t i = mark; i < ptrs.size(); ++i)
+            if (ptrs[i] && ptrs[i] != keep0 && ptrs[i] != keep1) { (void)hipFree(ptrs[i]); ptrs[i] = nullptr; }
+    }
+    bool ok() const { return !oom && err == hipSuccess; }
+};
+
+// The tree of build_bvh over n boxes, left on the device: nodes in pre-order (inner nodes
+// with start = end = 0) and the leaf primitive order.  Both belong to the arena.
+struct DevTree {
+    OutNode* nodes = nullptr;
+    uint32_t* order = nullptr;
+    uint32_t n_nodes = 0, depth = 0;
+};
+// bvh_build.hip: build_bvh_device without the copies.  d_boxes: n boxes (six doubles each,
+// list order) in device memory, 1 <= n <= 2^30.  Returns as build_bvh_device does; on
+// kDeviceBuildDone the builder's own scratch is already released and the stream is idle.
+int build_bvh_device_tree(Arena& m, const double* d_boxes, uint32_t n, uint32_t max_levels, DevTree& out,
+                          std::string& err);
+
+}  // namespace rt

@@ -36,6 +36,15 @@ RT_HD bool coord_fast(double v) {
     const double a = v < 0.0 ? -v : v;
     return a == 0.0 || (a >= 0x1p-397 && a <= 0x1p400);
 }
+// DevBvh::tri_q: a triangle edge component in the range of the split-division triangle
+// solve (rt_device.h tri_uvt_r): 0, or 2^-149 <= |v| < 2^129.
+RT_HD bool edge_ok(double v) {
+    const double a = fabs(v);
+    return a == 0.0 || (a >= 0x1p-149 && a < 0x1p129);
+}
+// The compact layout's condition (scene_build.cpp build_compact, bvh_emit.hip): the value
+// survives f64 -> f32 -> f64, and, for a coordinate, is no NaN.
+RT_HD bool f32_exact(double v) { return (double)(float)v == v || v != v; }
 RT_HD V3 mul(V3 a, V3 b) { return v3(a.x * b.x, a.y * b.y, a.z * b.z); }   // mul_element_wise
 RT_HD V3 div(V3 a, V3 b) { return v3(a.x / b.x, a.y / b.y, a.z / b.z); }   // div_element_wise
 RT_HD double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
@@ -45,6 +54,9 @@ RT_HD V3 cross(V3 a, V3 b) {
 RT_HD double magnitude(V3 a) { return sqrt(dot(a, a)); }
 RT_HD V3 normalize(V3 a) { return a * (1.0 / magnitude(a)); }
 RT_HD double comp(V3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
+RT_HD bool f32_exact3(V3 v) {
+    return f32_exact(v.x) && f32_exact(v.y) && f32_exact(v.z) && v.x == v.x && v.y == v.y && v.z == v.z;
+}
 RT_HD V3 load3(const double* p) { return v3(p[0], p[1], p[2]); }
 RT_HD void store3(double* p, V3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
 

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <thread>
 
@@ -291,7 +292,6 @@ static uint32_t shape_flags(const rt_shape& s, uint32_t& axis) {
 }
 
 struct ShapeItem { DevShape s; uint32_t mat; int32_t gid; Box3 box; };
-struct TriItem { Triangle t; V3 b, c; uint32_t mat; int32_t gid; Box3 box; };  // b, c: the vertices t was built from
 
 void build_shape_bvh(const std::vector<ShapeItem>& items, HostBvhArrays& out) {
     std::vector<Box3> boxes(items.size());
@@ -305,8 +305,6 @@ void build_shape_bvh(const std::vector<ShapeItem>& items, HostBvhArrays& out) {
         out.gid.push_back(items[i].gid);
     }
 }
-bool f32_exact(double v) { return (double)(float)v == v || v != v; }
-bool f32_exact3(V3 v) { return f32_exact(v.x) && f32_exact(v.y) && f32_exact(v.z) && v.x == v.x && v.y == v.y && v.z == v.z; }
 
 // Pair layout of the compact triangle BVH (rt_layout.h kPairFloats, DESIGN.md §4 "two
 // levels per line"): record c (one 128-B line per internal slot c) holds, for each child
@@ -446,7 +444,18 @@ void build_compact(const HostBvh& h, const std::vector<TriItem>& items, HostBvhA
 }
 
 std::string build_tri_bvh(const std::vector<TriItem>& items, HostBvhArrays& out, bool compact, TriBvhBuild tri_build,
-                          bool& device_built) {
+                          TriBvhEmit tri_emit, HostScene& scene) {
+    bool& device_built = scene.device_built;
+    if (tri_emit && !items.empty()) {  // build and records on the device; a fallback is the host's BVH
+        std::string err;
+        const int made = tri_emit(items, compact, out, err);
+        if (made == kDeviceBuildError) return err;
+        if (made == kDeviceBuildDone) {
+            device_built = scene.device_records = true;
+            return "";
+        }
+        tri_build = nullptr;
+    }
     std::vector<Box3> boxes(items.size());
     for (size_t i = 0; i < items.size(); ++i) boxes[i] = items[i].box;
     HostBvh h;
@@ -459,9 +468,7 @@ std::string build_tri_bvh(const std::vector<TriItem>& items, HostBvhArrays& out,
     if (compact && !h.nodes.empty()) build_compact(h, items, out);
     out.n_prims = (uint32_t)items.size();
     out.tris.reserve(items.size());
-    // DevBvh::tri_q: the edges' range of the split-division triangle solve
-    auto edge_ok = [](double v) { const double a = std::fabs(v); return a == 0.0 || (a >= 0x1p-149 && a < 0x1p129); };
-    out.tri_q = true;
+    out.tri_q = true;  // DevBvh::tri_q (rt_math.h edge_ok)
     for (const TriItem& it : items)
         for (double v : {it.t.ba.x, it.t.ba.y, it.t.ba.z, it.t.ca.x, it.t.ca.y, it.t.ca.z})
             out.tri_q = out.tri_q && edge_ok(v);
@@ -529,7 +536,7 @@ HostBvh build_bvh(const std::vector<Box3>& boxes) {
     return h;
 }
 
-std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_build) {
+std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_build, TriBvhEmit tri_emit) {
     auto t0 = std::chrono::steady_clock::now();
     if (d.n_materials == 0 && (d.n_shapes > 0 || d.n_triangles > 0)) return "scene has primitives but no materials";
     if (d.n_shapes > 0 && !d.shapes) return "shapes is NULL";
@@ -617,6 +624,10 @@ std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_
             it.box = bb;
         }
     }
+#ifdef RT_EMIT_TIMES
+    fprintf(stderr, "  items (host)        %8.1f ms\n",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+#endif
     // lights are copies of the emissive primitives (scene.rs:209-213, :229-241)
     std::vector<ShapeItem> lboxes, lells;
     std::vector<TriItem> ltris;
@@ -626,11 +637,11 @@ std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_
     build_shape_bvh(boxes, out.bvh[0]);
     build_shape_bvh(ells, out.bvh[1]);
     // the scene's triangle BVH: compact layout when exact
-    std::string err = build_tri_bvh(tris, out.bvh[2], true, tri_build, out.device_built);
+    std::string err = build_tri_bvh(tris, out.bvh[2], true, tri_build, tri_emit, out);
     if (!err.empty()) return err;
     build_shape_bvh(lboxes, out.bvh[3]);
     build_shape_bvh(lells, out.bvh[4]);
-    err = build_tri_bvh(ltris, out.bvh[5], false, tri_build, out.device_built);
+    err = build_tri_bvh(ltris, out.bvh[5], false, tri_build, tri_emit, out);
     if (!err.empty()) return err;
     out.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return "";

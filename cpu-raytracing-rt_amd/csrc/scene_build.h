@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rt_api.h"
@@ -51,9 +52,42 @@ enum { kDeviceBuildError = -1, kDeviceBuildFallback = 0, kDeviceBuildDone = 1 };
 constexpr uint32_t kDeviceBuildMaxLevels = 128;
 int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBvh& out, std::string& err);
 
+// One triangle of the scene in list order, as build_scene computes it.  bvh_emit.hip
+// uploads the vector as it is and reads the records by 16-byte loads, hence the alignment.
+struct alignas(16) TriItem { Triangle t; V3 b, c; uint32_t mat; int32_t gid; Box3 box; };  // b, c: the vertices t was built from
+static_assert(sizeof(TriItem) == 288 && std::is_trivially_copyable<TriItem>::value && std::is_standard_layout<TriItem>::value,
+              "TriItem is a POD of 36 eight-byte words (bvh_emit.hip indexes them)");
+
+// The arrays of a triangle BVH that bvh_emit.hip wrote on the device, in upload_bvh's
+// order: nodes, tris, tri_cold, tri_inv_area, mat, gid, cnodes, ctris, pnodes (null and 0
+// where the host vector would be empty).  Owns them until api.cpp adopts them into the scene.
+enum { kResNodes, kResTris, kResCold, kResInvArea, kResMat, kResGid, kResCnodes, kResCtris, kResPnodes, kResArrays };
+struct DevResident {
+    bool on = false;
+    mutable void* ptr[kResArrays] = {};  // adoption (api.cpp upload_bvh) takes the pointer and nulls it
+    uint64_t count[kResArrays] = {};     // elements
+    DevResident() = default;
+    DevResident(const DevResident&) = delete;
+    DevResident& operator=(const DevResident&) = delete;
+    ~DevResident() { reset(); }
+    void (*release)(void*) = nullptr;    // set by the emitter (hipFree); the host sources link without HIP
+    void reset() {                       // frees what was not adopted
+        for (void*& p : ptr) {
+            if (p && release) release(p);
+            p = nullptr;
+        }
+        for (uint64_t& c : count) c = 0;
+        on = false;
+    }
+};
+
 // Flattened scene ready for upload: every array is a host vector that maps
-// 1:1 onto a device allocation (see api.cpp).
+// 1:1 onto a device allocation (see api.cpp), or, for a triangle BVH emitted on the
+// device, an allocation that already exists (dev.on; the vectors are then empty).
 struct HostBvhArrays {
+    DevResident dev;
+    uint64_t count(int k, size_t host_size) const { return dev.on ? dev.count[k] : host_size; }
+    uint64_t n_nodes() const { return count(kResNodes, nodes.size()); }
     std::vector<DevNode> nodes;
     Box3 root;
     uint32_t n_prims = 0, depth = 0;
@@ -81,12 +115,21 @@ struct HostScene {
     HostBvhArrays bvh[6];   // boxes, ellipsoids, triangles, light boxes, light ellipsoids, light triangles
     double build_ms = 0.0;
     bool device_built = false;  // a triangle BVH came from build_bvh_device
+    bool device_records = false;  // a triangle BVH's arrays came from emit_tri_bvh_device
 };
 // tri_build: makes the two triangle BVHs and returns as build_bvh_device does (the host
 // builder runs on kDeviceBuildFallback); null: the host builder.  The small shape BVHs
 // are always the host's.
 using TriBvhBuild = int (*)(const std::vector<Box3>& boxes, HostBvh& out, std::string& err);
+// tri_emit: builds one non-empty triangle BVH and writes its final arrays on the device
+// (out.dev), returning as build_bvh_device does; on kDeviceBuildFallback that BVH takes the
+// host path.  compact: also the compact and pair layouts where build_compact would make them.
+using TriBvhEmit = int (*)(const std::vector<TriItem>& items, bool compact, HostBvhArrays& out, std::string& err);
+// bvh_emit.hip: the TriBvhEmit of the current HIP device (max_levels as build_bvh_device).
+int emit_tri_bvh_device(const std::vector<TriItem>& items, bool compact, uint32_t max_levels, HostBvhArrays& out,
+                        std::string& err);
 // Returns empty string on success, else an error message.
-std::string build_scene(const rt_scene_desc& desc, HostScene& out, TriBvhBuild tri_build = nullptr);
+std::string build_scene(const rt_scene_desc& desc, HostScene& out, TriBvhBuild tri_build = nullptr,
+                        TriBvhEmit tri_emit = nullptr);
 
 }  // namespace rt

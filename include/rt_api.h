@@ -170,8 +170,17 @@ int  rt_scene_create(const rt_scene_desc* desc, rt_scene** out);
    triangle and light-triangle BVHs are built on the current HIP device, the same trees
    byte for byte (rt_bvh_build_device; a BVH it cannot take is built on the host); the
    small shape BVHs stay on the host.  build_ms then covers the device build and the
-   copy back. */
+   copy back.
+   RT_BUILD_DEVICE_RECORDS (valid only with RT_BUILD_DEVICE, alone RT_ERR_INVALID): the
+   tree stays on the device and the triangle BVHs' arrays (nodes, triangle records, the
+   compact and pair layouts) are written there too, into the allocations the scene owns:
+   the same bytes as the host's (rt_scene_checksum agrees).  A BVH the device builder
+   cannot take, or whose arrays do not fit beside the build's scratch, takes the host
+   path, so a scene may mix.  build_ms then covers the device build and the emission;
+   upload_ms covers what is still copied from the host (shapes, materials, any host-built
+   BVH). */
 #define RT_BUILD_DEVICE 0x1u
+#define RT_BUILD_DEVICE_RECORDS 0x2u
 int  rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
 
@@ -182,8 +191,9 @@ typedef struct rt_scene_info {
     uint64_t n_light_triangles;
     uint64_t bvh_nodes[6];       /* boxes, ellipsoids, triangles, light boxes, light ellipsoids, light triangles */
     uint32_t bvh_depth[6];
-    double   build_ms;           /* BVH build (host, or device with RT_BUILD_DEVICE) */
-    double   upload_ms;          /* H2D copy                                      */
+    double   build_ms;           /* BVH build (host, or device with RT_BUILD_DEVICE; with
+                                    RT_BUILD_DEVICE_RECORDS also the record emission)  */
+    double   upload_ms;          /* H2D copy of what the host made                 */
     uint64_t device_bytes;       /* the scene's arrays; the per-launch workspace (commit
                                     ring, split-tail row buffer <= 256 MB, chunk partials
                                     <= 4 GiB, stack spill) is grow-only, sized by the
@@ -210,6 +220,9 @@ typedef struct rt_scene_info {
 /* RT_LAYOUT_DEVICE_BUILT: a triangle BVH of the scene was built on the device
    (rt_scene_create_ex with RT_BUILD_DEVICE); the arrays are the host build's */
 #define RT_LAYOUT_DEVICE_BUILT 0x8u
+/* RT_LAYOUT_DEVICE_RECORDS: at least one triangle BVH's arrays were written on the device
+   (RT_BUILD_DEVICE_RECORDS) rather than uploaded; RT_LAYOUT_DEVICE_BUILT is then set too */
+#define RT_LAYOUT_DEVICE_RECORDS 0x10u
 int rt_scene_get_info(const rt_scene* scene, rt_scene_info* out);
 /* Content hash of the scene's device arrays (BVHs, records, materials; not the
    per-launch workspace), computed on the scene's device.  Two handles built from the

@@ -4,8 +4,11 @@ device to device from devices[0]; prints each replica's upload_ms beside a plain
 rt_scene_create (what one replica's own host upload costs).  --build device builds that
 plain scene's triangle BVHs on the device (rt_scene_create_ex, RT_BUILD_DEVICE) and prints a
 second device-built scene's times too (the first one loads the builder's code object);
-rt_multi_create always builds on the host.
-    python tools/multi_create_time.py [WORKLOAD] [N] [--build host|device]"""
+--records device (with --build device) also writes the triangle BVHs' arrays on the device
+(RT_BUILD_DEVICE_RECORDS); --runs K times K scenes after that warm-up one; --no-multi stops
+before rt_multi_create, which always builds on the host.
+    python tools/multi_create_time.py [WORKLOAD] [N] [--build host|device] [--records host|device]
+                                      [--runs K] [--no-multi]"""
 import os
 import sys
 import time
@@ -18,25 +21,38 @@ import bench  # noqa: E402
 from conftest import load_package  # noqa: E402
 
 rt = load_package()
-build = "host"
-if "--build" in sys.argv:
-    k = sys.argv.index("--build")
-    build = sys.argv[k + 1]
+
+
+def option(name, default):
+    if name not in sys.argv:
+        return default
+    k = sys.argv.index(name)
+    value = sys.argv[k + 1]
     del sys.argv[k:k + 2]
+    return value
+
+
+build, records, runs = option("--build", "host"), option("--records", "host"), int(option("--runs", "1"))
+no_multi = "--no-multi" in sys.argv
+if no_multi:
+    sys.argv.remove("--no-multi")
 wl = sys.argv[1] if len(sys.argv) > 1 else "C5"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 scene_file, W, H, spp, _ = bench.WORKLOADS[wl]
 desc, params = bench.load_workload(rt, scene_file, W, H, spp)
-for _ in range(2 if build == "device" else 1):
+for _ in range(runs + 1 if build == "device" else runs):
     t = time.perf_counter()
-    s = rt.Scene(desc, build=build)
+    s = rt.Scene(desc, build=build, records=records)
     one = time.perf_counter() - t
     i0 = s.info()
     if build == "device":
         assert i0["layout_flags"] & rt.RT_LAYOUT_DEVICE_BUILT
-    print(f"{wl}: rt_scene_create ({build} build) {one * 1e3:.0f} ms (build {i0['build_ms']:.0f} ms, host upload {i0['upload_ms']:.1f} ms, "
+    assert bool(i0["layout_flags"] & rt.RT_LAYOUT_DEVICE_RECORDS) == (records == "device")
+    print(f"{wl}: rt_scene_create ({build} build, {records} records) {one * 1e3:.0f} ms (build {i0['build_ms']:.0f} ms, host upload {i0['upload_ms']:.1f} ms, "
           f"{i0['device_bytes'] / 1e9:.3f} GB)", flush=True)
     del s
+if no_multi:
+    sys.exit(0)
 t = time.perf_counter()
 m = rt.MultiScene(desc, [0] * n, peer=True)
 tot = time.perf_counter() - t
