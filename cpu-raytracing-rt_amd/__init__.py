@@ -113,8 +113,10 @@ RT_LAYOUT_COMPACT_TRIS = 0x1
 RT_LAYOUT_PAIR_NODES = 0x4
 RT_LAYOUT_DEVICE_BUILT = 0x8
 RT_LAYOUT_DEVICE_RECORDS = 0x10
+RT_LAYOUT_DEVICE_ITEMS = 0x20
 RT_BUILD_DEVICE = 0x1
 RT_BUILD_DEVICE_RECORDS = 0x2
+RT_BUILD_DEVICE_ITEMS = 0x4
 
 
 # every symbol include/rt_api.h declares (checked by tests/test_abi.py)
@@ -356,19 +358,25 @@ def load_gltf(path: str, width: int, height: int, spp: int):
 class Scene:
     """Scene::new: BVHs built on the host (build="device": the triangle BVHs on the current
     HIP device, the same trees; records="device": their arrays written there too, not
-    uploaded), flattened arrays resident on the current HIP device."""
+    uploaded; items="device": the per-triangle items behind those arrays computed there from
+    the description's arrays), flattened arrays resident on the current HIP device."""
 
-    def __init__(self, desc: SceneDesc, build: str = "host", records: str = "host"):
+    def __init__(self, desc: SceneDesc, build: str = "host", records: str = "host", items: str = "host"):
         if build not in ("host", "device"):
             raise ValueError(f"build must be 'host' or 'device', not {build!r}")
         if records not in ("host", "device"):
             raise ValueError(f"records must be 'host' or 'device', not {records!r}")
         if records == "device" and build != "device":
             raise ValueError("records='device' needs build='device'")
+        if items not in ("host", "device"):
+            raise ValueError(f"items must be 'host' or 'device', not {items!r}")
+        if items == "device" and records != "device":
+            raise ValueError("items='device' needs build='device' and records='device'")
         self.desc = desc
         d, keep = desc.to_c()
         h = C.c_void_p()
-        flags = (RT_BUILD_DEVICE if build == "device" else 0) | (RT_BUILD_DEVICE_RECORDS if records == "device" else 0)
+        flags = ((RT_BUILD_DEVICE if build == "device" else 0) | (RT_BUILD_DEVICE_RECORDS if records == "device" else 0) |
+                 (RT_BUILD_DEVICE_ITEMS if items == "device" else 0))
         _check(lib().rt_scene_create_ex(C.byref(d), flags, C.byref(h)))
         self._h = h
         del keep

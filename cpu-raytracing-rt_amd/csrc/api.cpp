@@ -554,7 +554,10 @@ int rt_device_count(void) {
 int rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out) {
     if (!desc || !out) return set_error(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
-    if (build_flags & ~(RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS)) return set_error(RT_ERR_INVALID, "unknown build flag");
+    if (build_flags & ~(RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS | RT_BUILD_DEVICE_ITEMS))
+        return set_error(RT_ERR_INVALID, "unknown build flag");
+    if ((build_flags & RT_BUILD_DEVICE_ITEMS) && !(build_flags & RT_BUILD_DEVICE_RECORDS))
+        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_ITEMS needs RT_BUILD_DEVICE_RECORDS (the items feed the device's record emission)");
     if ((build_flags & RT_BUILD_DEVICE_RECORDS) && !(build_flags & RT_BUILD_DEVICE))
         return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_RECORDS needs RT_BUILD_DEVICE (the records come from the device's tree)");
     HostScene hs;
@@ -574,12 +577,18 @@ static int tri_emit_device(const std::vector<TriItem>& items, bool compact, Host
     return emit_tri_bvh_device(items, compact, 0, out, err);
 }
 
+static int tri_items_device(const rt_scene_desc& desc, HostBvhArrays& tris, HostBvhArrays& ltris, TriItemsOutcome& res,
+                            std::string& err) {
+    return emit_tri_bvhs_device_items(desc, 0, tris, ltris, res, err);
+}
+
 int scene_build_host(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags) {
     int ndev = 0;
     if ((build_flags & RT_BUILD_DEVICE) && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0))
         return set_error(RT_ERR_DEVICE, "no HIP device visible (RT_BUILD_DEVICE builds on one)");
     std::string err = build_scene(desc, hs, (build_flags & RT_BUILD_DEVICE) ? tri_build_device : nullptr,
-                                  (build_flags & RT_BUILD_DEVICE_RECORDS) ? tri_emit_device : nullptr);
+                                  (build_flags & RT_BUILD_DEVICE_RECORDS) ? tri_emit_device : nullptr,
+                                  (build_flags & RT_BUILD_DEVICE_ITEMS) ? tri_items_device : nullptr);
     if (!err.empty()) return set_error(RT_ERR_INVALID, err);
     for (int k = 0; k < 6; ++k)  // traversal stack words carry node indices in 30 bits (render.hip child_word)
         if (hs.bvh[k].n_nodes() >= (1u << 30)) return set_error(RT_ERR_INVALID, "BVH exceeds 2^30 nodes");
@@ -672,7 +681,8 @@ int scene_upload(const HostScene& hs, rt_scene** out, bool replica) {
     s->pair_bytes = (T.count(kResPnodes, T.pnodes.size()) + n_ctris) * sizeof(float);
     s->info.layout_flags = (d.tris.cnodes ? RT_LAYOUT_COMPACT_TRIS : 0u) | (d.lq_boxes ? RT_LAYOUT_LQ_SKIP : 0u) |
                            (d.tris.pnodes ? RT_LAYOUT_PAIR_NODES : 0u) | (hs.device_built ? RT_LAYOUT_DEVICE_BUILT : 0u) |
-                           (hs.device_records ? RT_LAYOUT_DEVICE_RECORDS : 0u);
+                           (hs.device_records ? RT_LAYOUT_DEVICE_RECORDS : 0u) |
+                           (hs.device_items ? RT_LAYOUT_DEVICE_ITEMS : 0u);
     s->info.build_ms = hs.build_ms;
     s->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = owner.release();

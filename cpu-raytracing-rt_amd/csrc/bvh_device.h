@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -52,4 +54,27 @@ struct DevTree {
 int build_bvh_device_tree(Arena& m, const double* d_boxes, uint32_t n, uint32_t max_levels, DevTree& out,
                           std::string& err);
 
+// bvh_emit.hip: emit_tri_bvh_device behind its upload.  d_items (n triangles in list order)
+// and d_boxes (their boxes, six doubles each) are device memory of the caller's arena;
+// d_boxes is released once the tree stands, and whatever the call itself took from the
+// arena is released before it returns, so a caller may emit several BVHs in turn.  Returns
+// as emit_tri_bvh_device does (n == 0: kDeviceBuildFallback).
+int emit_tri_bvh_device_core(Arena& m, const TriItem* d_items, double* d_boxes, uint32_t n, bool compact,
+                             uint32_t max_levels, HostBvhArrays& out, std::string& err);
+
 }  // namespace rt
+
+// -DRT_EMIT_TIMES (a variant build): the wall time of each phase of an emission on stderr
+#ifdef RT_EMIT_TIMES
+#define RT_EMIT_MARK_START() auto mark_ = std::chrono::steady_clock::now()
+#define RT_EMIT_MARK(name)                                                                         \
+    do {                                                                                           \
+        (void)hipDeviceSynchronize();                                                              \
+        const auto now_ = std::chrono::steady_clock::now();                                        \
+        fprintf(stderr, "  emit %-14s %8.1f ms\n", name, std::chrono::duration<double, std::milli>(now_ - mark_).count()); \
+        mark_ = now_;                                                                              \
+    } while (0)
+#else
+#define RT_EMIT_MARK_START() do {} while (0)
+#define RT_EMIT_MARK(name) do {} while (0)
+#endif

@@ -419,18 +419,7 @@ inline uint32_t blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 
 
 }  // namespace
 
-// -DRT_EMIT_TIMES (a variant build): the wall time of each phase of an emission on stderr
-#ifdef RT_EMIT_TIMES
-#define BE_MARK(name)                                                                              \
-    do {                                                                                           \
-        (void)hipDeviceSynchronize();                                                              \
-        const auto now_ = std::chrono::steady_clock::now();                                        \
-        fprintf(stderr, "  emit %-14s %8.1f ms\n", name, std::chrono::duration<double, std::milli>(now_ - mark_).count()); \
-        mark_ = now_;                                                                              \
-    } while (0)
-#else
-#define BE_MARK(name) do {} while (0)
-#endif
+#define BE_MARK(name) RT_EMIT_MARK(name)
 #define BE_TRY(call)                                                         \
     do {                                                                     \
         const hipError_t e_ = (call);                                        \
@@ -441,30 +430,12 @@ inline uint32_t blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 
         if (!m.ok()) { if (m.oom) return kDeviceBuildFallback; BE_TRY(m.err); } \
     } while (0)
 
-int emit_tri_bvh_device(const std::vector<TriItem>& items, bool compact, uint32_t max_levels, HostBvhArrays& out,
-                        std::string& err) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        err = "no HIP device visible (the device builder needs one)";
-        return kDeviceBuildError;
-    }
-    const uint64_t n64 = items.size();
-    if (n64 == 0 || n64 > kMaxPrims) return kDeviceBuildFallback;
-    const uint32_t n = (uint32_t)n64;
-    const hipStream_t st = 0;
-    Arena m;
-#ifdef RT_EMIT_TIMES
-    auto mark_ = std::chrono::steady_clock::now();
-#endif
+namespace {
 
-    // the triangles as they are, once; the builder's boxes out of them; the tree
-    TriItem* d_items = m.get<TriItem>(n);
-    double* d_boxes = m.get<double>((size_t)n * 6);
-    BE_SCRATCH_OK();
-    BE_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n * sizeof(TriItem), hipMemcpyHostToDevice, st));
-    be_boxes<<<blocks((uint64_t)n * 6, kThreads), kThreads, 0, st>>>((const u64*)d_items, n, (u64*)d_boxes);
-    BE_TRY(hipGetLastError());
-    BE_MARK("item upload");
+int emit_core(Arena& m, const TriItem* d_items, double* d_boxes, uint32_t n, bool compact, uint32_t max_levels,
+              HostBvhArrays& out, std::string& err) {
+    const hipStream_t st = 0;
+    RT_EMIT_MARK_START();
     DevTree t;
     const int made = build_bvh_device_tree(m, d_boxes, n, max_levels, t, err);
     if (made != kDeviceBuildDone) return made;
@@ -546,6 +517,42 @@ int emit_tri_bvh_device(const std::vector<TriItem>& items, bool compact, uint32_
     out.fast = (h.flags & kFlagFast) != 0;
     out.tri_q = (h.flags & kFlagTriQ) != 0;
     return kDeviceBuildDone;
+}
+
+}  // namespace
+
+int emit_tri_bvh_device_core(Arena& m, const TriItem* d_items, double* d_boxes, uint32_t n, bool compact,
+                             uint32_t max_levels, HostBvhArrays& out, std::string& err) {
+    if (n == 0 || n > kMaxPrims) return kDeviceBuildFallback;
+    const size_t mark = m.ptrs.size();
+    const int made = emit_core(m, d_items, d_boxes, n, compact, max_levels, out, err);
+    m.release_since(mark, nullptr, nullptr);  // the tree and the tables: the caller's next BVH gets the room
+    return made;
+}
+
+int emit_tri_bvh_device(const std::vector<TriItem>& items, bool compact, uint32_t max_levels, HostBvhArrays& out,
+                        std::string& err) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        err = "no HIP device visible (the device builder needs one)";
+        return kDeviceBuildError;
+    }
+    const uint64_t n64 = items.size();
+    if (n64 == 0 || n64 > kMaxPrims) return kDeviceBuildFallback;
+    const uint32_t n = (uint32_t)n64;
+    const hipStream_t st = 0;
+    Arena m;
+    RT_EMIT_MARK_START();
+
+    // the triangles as they are, once; the builder's boxes out of them
+    TriItem* d_items = m.get<TriItem>(n);
+    double* d_boxes = m.get<double>((size_t)n * 6);
+    BE_SCRATCH_OK();
+    BE_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n * sizeof(TriItem), hipMemcpyHostToDevice, st));
+    be_boxes<<<blocks((uint64_t)n * 6, kThreads), kThreads, 0, st>>>((const u64*)d_items, n, (u64*)d_boxes);
+    BE_TRY(hipGetLastError());
+    BE_MARK("item upload");
+    return emit_tri_bvh_device_core(m, d_items, d_boxes, n, compact, max_levels, out, err);
 }
 
 }  // namespace rt

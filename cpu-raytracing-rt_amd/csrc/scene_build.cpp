@@ -21,28 +21,6 @@
 
 namespace rt {
 
-Triangle triangle_props(V3 a, V3 b, V3 c) {
-    Triangle t;
-    t.a = a;
-    t.ba = b - a;
-    t.ca = c - a;
-    V3 sized = cross(t.ba, t.ca);
-    double area = sqrt(dot(sized, sized)) / 2.0;
-    t.ng = normalize(sized);
-    t.inv_area = 1.0 / area;
-    return t;
-}
-Triangle triangle_smooth(V3 a, V3 b, V3 c, V3 na, V3 nb, V3 nc) {
-    Triangle t = triangle_props(a, b, c);
-    t.na = na; t.nb = nb; t.nc = nc;
-    return t;
-}
-Triangle triangle_geometric(V3 a, V3 b, V3 c) {
-    Triangle t = triangle_props(a, b, c);
-    t.na = t.ng; t.nb = t.ng; t.nc = t.ng;
-    return t;
-}
-
 namespace {
 
 Box3 rotated_box(const Box3& b, Quat r) {  // scene.rs:255-268
@@ -536,7 +514,8 @@ HostBvh build_bvh(const std::vector<Box3>& boxes) {
     return h;
 }
 
-std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_build, TriBvhEmit tri_emit) {
+std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_build, TriBvhEmit tri_emit,
+                        TriBvhItems tri_items) {
     auto t0 = std::chrono::steady_clock::now();
     if (d.n_materials == 0 && (d.n_shapes > 0 || d.n_triangles > 0)) return "scene has primitives but no materials";
     if (d.n_shapes > 0 && !d.shapes) return "shapes is NULL";
@@ -592,56 +571,52 @@ std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_
         it.box = w;
         (s.type == RT_SHAPE_BOX ? boxes : ells).push_back(it);
     }
-    std::vector<TriItem> tris(d.n_triangles);
-    for (uint64_t j = 0; j < d.n_triangles; ++j) {
-        const double* v = d.tri_vertices + 9 * j;
-        TriItem& it = tris[j];
-        it.mat = d.tri_material[j];
-        if (it.mat >= d.n_materials) return "triangle material out of range";
-        it.gid = (int32_t)(d.n_shapes + j);
-        if (d.tri_mode == RT_TRI_GLTF) {  // new_with_smooth_normal + instantiate (gltf/scene_builder.rs:42-55)
-            const double* nn = d.tri_normals + 9 * j;
-            it.t = triangle_smooth(load3(v), load3(v + 3), load3(v + 6), load3(nn), load3(nn + 3), load3(nn + 6));
-            it.b = load3(v + 3);
-            it.c = load3(v + 6);
-            Box3 b = box_empty();
-            box_extend(b, it.t.a);
-            box_extend(b, it.t.a + it.t.ba);
-            box_extend(b, it.t.a + it.t.ca);
-            it.box = b;
-        } else {  // new_with_geometry_normals (scene_parser.rs:71-73) + TrianglePrimitive::new (scene.rs:139-165)
-            Triangle m = triangle_geometric(load3(v), load3(v + 3), load3(v + 6));
-            V3 pos = d.tri_position ? load3(d.tri_position + 3 * j) : v3(0, 0, 0);
-            Quat rot = d.tri_rotation ? load_quat(d.tri_rotation + 4 * j) : Quat{1.0, v3(0, 0, 0)};
-            V3 a = rotate(rot, m.a) + pos;
-            V3 b = rotate(rot, m.ba + m.a) + pos;
-            V3 c = rotate(rot, m.ca + m.a) + pos;
-            it.t = triangle_smooth(a, b, c, rotate(rot, m.na), rotate(rot, m.nb), rotate(rot, m.nc));
-            it.b = b;
-            it.c = c;
-            Box3 bb = box_empty();
-            box_extend(bb, a); box_extend(bb, b); box_extend(bb, c);
-            it.box = bb;
+    // The triangle items (tri_items.h): on the host here, or, with tri_items, on the device,
+    // and then here only for a triangle BVH that the device path left to the host.
+    std::vector<TriItem> tris;
+    auto host_items = [&]() -> const char* {
+        auto t1 = std::chrono::steady_clock::now();
+        tris.resize(d.n_triangles);
+        for (uint64_t j = 0; j < d.n_triangles; ++j) {
+            if (d.tri_material[j] >= d.n_materials) return "triangle material out of range";
+            tri_item_of(d, j, tris[j]);
         }
-    }
 #ifdef RT_EMIT_TIMES
-    fprintf(stderr, "  items (host)        %8.1f ms\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        fprintf(stderr, "  items (host)        %8.1f ms\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
 #endif
+        (void)t1;
+        return nullptr;
+    };
+    TriItemsOutcome dev;
+    const bool on_device = tri_items && d.n_triangles > 0;
+    if (on_device) {
+        for (uint64_t j = 0; j < d.n_triangles; ++j)
+            if (d.tri_material[j] >= d.n_materials) return "triangle material out of range";
+        std::string err;
+        if (tri_items(d, out.bvh[2], out.bvh[5], dev, err) == kDeviceBuildError) return err;
+        for (int made : dev.made)
+            if (made == kDeviceBuildDone) out.device_built = out.device_records = out.device_items = true;
+    }
+    const bool tris_done = dev.made[0] == kDeviceBuildDone;
+    const bool ltris_done = dev.made[1] == kDeviceBuildDone || (on_device && dev.n_light == 0);  // no lights: no items needed
+    if (!tris_done || !ltris_done)
+        if (const char* e = host_items()) return e;
     // lights are copies of the emissive primitives (scene.rs:209-213, :229-241)
     std::vector<ShapeItem> lboxes, lells;
     std::vector<TriItem> ltris;
     for (auto& it : boxes) if (is_light(d.materials[it.mat])) lboxes.push_back(it);
     for (auto& it : ells) if (is_light(d.materials[it.mat])) lells.push_back(it);
-    for (auto& it : tris) if (is_light(d.materials[it.mat])) ltris.push_back(it);
+    if (dev.made[1] != kDeviceBuildDone)
+        for (auto& it : tris) if (is_light(d.materials[it.mat])) ltris.push_back(it);
     build_shape_bvh(boxes, out.bvh[0]);
     build_shape_bvh(ells, out.bvh[1]);
     // the scene's triangle BVH: compact layout when exact
-    std::string err = build_tri_bvh(tris, out.bvh[2], true, tri_build, tri_emit, out);
+    std::string err = tris_done ? "" : build_tri_bvh(tris, out.bvh[2], true, tri_build, tri_emit, out);
     if (!err.empty()) return err;
     build_shape_bvh(lboxes, out.bvh[3]);
     build_shape_bvh(lells, out.bvh[4]);
-    err = build_tri_bvh(ltris, out.bvh[5], false, tri_build, tri_emit, out);
+    if (dev.made[1] != kDeviceBuildDone) err = build_tri_bvh(ltris, out.bvh[5], false, tri_build, tri_emit, out);
     if (!err.empty()) return err;
     out.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return "";

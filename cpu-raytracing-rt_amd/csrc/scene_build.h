@@ -5,23 +5,14 @@
 #include <stdint.h>
 
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/rt_api.h"
 #include "rt_layout.h"
 #include "rt_math.h"
+#include "tri_items.h"
 
 namespace rt {
-
-struct Triangle {            // triangle.rs:5-17
-    V3 a, ba, ca, ng;
-    double inv_area;
-    V3 na, nb, nc;
-};
-Triangle triangle_props(V3 a, V3 b, V3 c);                          // triangle.rs:41-47
-Triangle triangle_smooth(V3 a, V3 b, V3 c, V3 na, V3 nb, V3 nc);    // triangle.rs:20-23
-Triangle triangle_geometric(V3 a, V3 b, V3 c);                      // triangle.rs:25-28
 
 // One BVH in host form: pre-order nodes + primitive permutation.
 struct HostNode {
@@ -52,11 +43,22 @@ enum { kDeviceBuildError = -1, kDeviceBuildFallback = 0, kDeviceBuildDone = 1 };
 constexpr uint32_t kDeviceBuildMaxLevels = 128;
 int build_bvh_device(const std::vector<Box3>& boxes, uint32_t max_levels, HostBvh& out, std::string& err);
 
-// One triangle of the scene in list order, as build_scene computes it.  bvh_emit.hip
-// uploads the vector as it is and reads the records by 16-byte loads, hence the alignment.
-struct alignas(16) TriItem { Triangle t; V3 b, c; uint32_t mat; int32_t gid; Box3 box; };  // b, c: the vertices t was built from
-static_assert(sizeof(TriItem) == 288 && std::is_trivially_copyable<TriItem>::value && std::is_standard_layout<TriItem>::value,
-              "TriItem is a POD of 36 eight-byte words (bvh_emit.hip indexes them)");
+// Triangle j of the description (arrays and material index already checked) as
+// build_scene's item: tri_items.h's arithmetic, mat and gid.  The device's fix-up list
+// (tri_items.hip) recomputes its items with this too.
+inline void tri_item_of(const rt_scene_desc& d, uint64_t j, TriItem& it) {
+    const double* v = d.tri_vertices + 9 * j;
+    it.mat = d.tri_material[j];
+    it.gid = (int32_t)(d.n_shapes + j);
+    if (d.tri_mode == RT_TRI_GLTF) {
+        const double* nn = d.tri_normals + 9 * j;
+        tri_item_gltf(load3(v), load3(v + 3), load3(v + 6), load3(nn), load3(nn + 3), load3(nn + 6), it);
+    } else {
+        const V3 pos = d.tri_position ? load3(d.tri_position + 3 * j) : v3(0, 0, 0);
+        const Quat rot = d.tri_rotation ? load_quat(d.tri_rotation + 4 * j) : Quat{1.0, v3(0, 0, 0)};
+        tri_item_custom(load3(v), load3(v + 3), load3(v + 6), pos, rot, it);
+    }
+}
 
 // The arrays of a triangle BVH that bvh_emit.hip wrote on the device, in upload_bvh's
 // order: nodes, tris, tri_cold, tri_inv_area, mat, gid, cnodes, ctris, pnodes (null and 0
@@ -116,6 +118,7 @@ struct HostScene {
     double build_ms = 0.0;
     bool device_built = false;  // a triangle BVH came from build_bvh_device
     bool device_records = false;  // a triangle BVH's arrays came from emit_tri_bvh_device
+    bool device_items = false;  // ... emitted from items computed on the device (tri_items.hip)
 };
 // tri_build: makes the two triangle BVHs and returns as build_bvh_device does (the host
 // builder runs on kDeviceBuildFallback); null: the host builder.  The small shape BVHs
@@ -128,8 +131,20 @@ using TriBvhEmit = int (*)(const std::vector<TriItem>& items, bool compact, Host
 // bvh_emit.hip: the TriBvhEmit of the current HIP device (max_levels as build_bvh_device).
 int emit_tri_bvh_device(const std::vector<TriItem>& items, bool compact, uint32_t max_levels, HostBvhArrays& out,
                         std::string& err);
+// tri_items: computes the items of all the description's triangles (n_triangles > 0, arrays
+// and material indices checked) on the device and emits both triangle BVHs from them.
+// made[0] is bvh[2]'s outcome (tris, with the compact layouts), made[1] bvh[5]'s (ltris),
+// each as build_bvh_device returns; a BVH left at kDeviceBuildFallback takes the tri_emit /
+// tri_build / host chain with items computed on the host.  n_light: the number of light
+// triangles, or UINT64_MAX where the device did not get to count them.
+struct TriItemsOutcome { int made[2] = {kDeviceBuildFallback, kDeviceBuildFallback}; uint64_t n_light = UINT64_MAX; };
+using TriBvhItems = int (*)(const rt_scene_desc& desc, HostBvhArrays& tris, HostBvhArrays& ltris, TriItemsOutcome& res,
+                            std::string& err);
+// tri_items.hip: the TriBvhItems of the current HIP device.
+int emit_tri_bvhs_device_items(const rt_scene_desc& desc, uint32_t max_levels, HostBvhArrays& tris,
+                               HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err);
 // Returns empty string on success, else an error message.
 std::string build_scene(const rt_scene_desc& desc, HostScene& out, TriBvhBuild tri_build = nullptr,
-                        TriBvhEmit tri_emit = nullptr);
+                        TriBvhEmit tri_emit = nullptr, TriBvhItems tri_items = nullptr);
 
 }  // namespace rt

@@ -178,9 +178,19 @@ int  rt_scene_create(const rt_scene_desc* desc, rt_scene** out);
    cannot take, or whose arrays do not fit beside the build's scratch, takes the host
    path, so a scene may mix.  build_ms then covers the device build and the emission;
    upload_ms covers what is still copied from the host (shapes, materials, any host-built
-   BVH). */
+   BVH).
+   RT_BUILD_DEVICE_ITEMS (valid only with RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS, else
+   RT_ERR_INVALID): the per-triangle items those records are made from (the triangle's
+   edges, geometric normal and inverse area, a custom-format triangle's rotation and
+   translation, its box) are computed on the device from the description's arrays, which
+   are uploaded in place of the finished items; the light-triangle BVH's items are picked
+   out of them there.  The same bytes again: a triangle with a NaN among its inputs or
+   results is recomputed on the host (up to 65,536 of them; a scene with more computes all
+   its items on the host), and a BVH the device path cannot take gets host items and the
+   path above.  The argument checks and their messages are the host's. */
 #define RT_BUILD_DEVICE 0x1u
 #define RT_BUILD_DEVICE_RECORDS 0x2u
+#define RT_BUILD_DEVICE_ITEMS 0x4u
 int  rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
 
@@ -192,7 +202,8 @@ typedef struct rt_scene_info {
     uint64_t bvh_nodes[6];       /* boxes, ellipsoids, triangles, light boxes, light ellipsoids, light triangles */
     uint32_t bvh_depth[6];
     double   build_ms;           /* BVH build (host, or device with RT_BUILD_DEVICE; with
-                                    RT_BUILD_DEVICE_RECORDS also the record emission)  */
+                                    RT_BUILD_DEVICE_RECORDS also the record emission, with
+                                    RT_BUILD_DEVICE_ITEMS the description's upload too) */
     double   upload_ms;          /* H2D copy of what the host made                 */
     uint64_t device_bytes;       /* the scene's arrays; the per-launch workspace (commit
                                     ring, split-tail row buffer <= 256 MB, chunk partials
@@ -223,6 +234,10 @@ typedef struct rt_scene_info {
 /* RT_LAYOUT_DEVICE_RECORDS: at least one triangle BVH's arrays were written on the device
    (RT_BUILD_DEVICE_RECORDS) rather than uploaded; RT_LAYOUT_DEVICE_BUILT is then set too */
 #define RT_LAYOUT_DEVICE_RECORDS 0x10u
+/* RT_LAYOUT_DEVICE_ITEMS: at least one triangle BVH's arrays were written from items
+   computed on the device (RT_BUILD_DEVICE_ITEMS); RT_LAYOUT_DEVICE_RECORDS and
+   RT_LAYOUT_DEVICE_BUILT are then set too */
+#define RT_LAYOUT_DEVICE_ITEMS 0x20u
 int rt_scene_get_info(const rt_scene* scene, rt_scene_info* out);
 /* Content hash of the scene's device arrays (BVHs, records, materials; not the
    per-launch workspace), computed on the scene's device.  Two handles built from the

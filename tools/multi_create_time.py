@@ -5,10 +5,11 @@ rt_scene_create (what one replica's own host upload costs).  --build device buil
 plain scene's triangle BVHs on the device (rt_scene_create_ex, RT_BUILD_DEVICE) and prints a
 second device-built scene's times too (the first one loads the builder's code object);
 --records device (with --build device) also writes the triangle BVHs' arrays on the device
-(RT_BUILD_DEVICE_RECORDS); --runs K times K scenes after that warm-up one; --no-multi stops
+(RT_BUILD_DEVICE_RECORDS); --items device (with both) computes the per-triangle items there
+too (RT_BUILD_DEVICE_ITEMS); --runs K times K scenes after that warm-up one; --no-multi stops
 before rt_multi_create, which always builds on the host.
     python tools/multi_create_time.py [WORKLOAD] [N] [--build host|device] [--records host|device]
-                                      [--runs K] [--no-multi]"""
+                                      [--items host|device] [--runs K] [--no-multi]"""
 import os
 import sys
 import time
@@ -33,6 +34,7 @@ def option(name, default):
 
 
 build, records, runs = option("--build", "host"), option("--records", "host"), int(option("--runs", "1"))
+items = option("--items", "host")
 no_multi = "--no-multi" in sys.argv
 if no_multi:
     sys.argv.remove("--no-multi")
@@ -42,13 +44,14 @@ scene_file, W, H, spp, _ = bench.WORKLOADS[wl]
 desc, params = bench.load_workload(rt, scene_file, W, H, spp)
 for _ in range(runs + 1 if build == "device" else runs):
     t = time.perf_counter()
-    s = rt.Scene(desc, build=build, records=records)
+    s = rt.Scene(desc, build=build, records=records, items=items)
     one = time.perf_counter() - t
     i0 = s.info()
     if build == "device":
         assert i0["layout_flags"] & rt.RT_LAYOUT_DEVICE_BUILT
     assert bool(i0["layout_flags"] & rt.RT_LAYOUT_DEVICE_RECORDS) == (records == "device")
-    print(f"{wl}: rt_scene_create ({build} build, {records} records) {one * 1e3:.0f} ms (build {i0['build_ms']:.0f} ms, host upload {i0['upload_ms']:.1f} ms, "
+    assert bool(i0["layout_flags"] & rt.RT_LAYOUT_DEVICE_ITEMS) == (items == "device")
+    print(f"{wl}: rt_scene_create ({build} build, {records} records, {items} items) {one * 1e3:.0f} ms (build {i0['build_ms']:.0f} ms, host upload {i0['upload_ms']:.1f} ms, "
           f"{i0['device_bytes'] / 1e9:.3f} GB)", flush=True)
     del s
 if no_multi:
