@@ -114,15 +114,19 @@ RT_LAYOUT_PAIR_NODES = 0x4
 RT_LAYOUT_DEVICE_BUILT = 0x8
 RT_LAYOUT_DEVICE_RECORDS = 0x10
 RT_LAYOUT_DEVICE_ITEMS = 0x20
+RT_LAYOUT_DEVICE_MESHES = 0x40
 RT_BUILD_DEVICE = 0x1
 RT_BUILD_DEVICE_RECORDS = 0x2
 RT_BUILD_DEVICE_ITEMS = 0x4
+RT_BUILD_DEVICE_MESHES = 0x8
+RT_GLTF_DEFER = 0x1
 
 
 # every symbol include/rt_api.h declares (checked by tests/test_abi.py)
 EXPORTS = {
     "rt_scene_create": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_void_p)]),
     "rt_scene_create_ex": (C.c_int, [C.POINTER(rt_scene_desc), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rt_scene_create_parsed": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_scene_destroy": (None, [C.c_void_p]),
     "rt_scene_get_info": (C.c_int, [C.c_void_p, C.POINTER(rt_scene_info)]),
     "rt_scene_checksum": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -148,6 +152,7 @@ EXPORTS = {
     "rt_intersect_lights_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_parse_custom_scene": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "rt_load_gltf": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rt_load_gltf_ex": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_parsed_scene_get": (C.c_int, [C.c_void_p, C.POINTER(rt_scene_desc), C.POINTER(rt_render_params)]),
     "rt_parsed_scene_free": (None, [C.c_void_p]),
     "rt_tonemap_gamma": (None, [C.c_void_p, C.c_uint64, C.c_void_p]),
@@ -348,9 +353,49 @@ def parse_scene(text: str):
     return _take_parsed(h)
 
 
-def load_gltf(path: str, width: int, height: int, spp: int):
-    """gltf::parse + gltf::build_scene (main.rs:47-66) -> (SceneDesc, RenderParams)."""
+class ParsedScene:
+    """A deferred glTF parse (rt_load_gltf_ex, RT_GLTF_DEFER): the draw plan and the buffers'
+    bytes.  ``params`` is there at once; ``desc()`` makes the SceneDesc on first use (the
+    host flatten) and raises what the eager load would have raised.  Owns the handle until
+    ``close()``."""
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+        self._desc = None
+        p = rt_render_params()
+        _check(lib().rt_parsed_scene_get(handle, None, C.byref(p)))
+        self.params = RenderParams.from_c(p)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def desc(self) -> "SceneDesc":
+        if self._desc is None:
+            d = rt_scene_desc()
+            _check(lib().rt_parsed_scene_get(self._h, C.byref(d), None))
+            self._desc = _desc_from_c(d)
+        return self._desc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rt_parsed_scene_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_gltf(path: str, width: int, height: int, spp: int, defer: bool = False):
+    """gltf::parse + gltf::build_scene (main.rs:47-66) -> (SceneDesc, RenderParams); with
+    defer=True a ParsedScene, whose meshes Scene.from_parsed can flatten on the device."""
     h = C.c_void_p()
+    if defer:
+        _check(lib().rt_load_gltf_ex(path.encode(), width, height, spp, RT_GLTF_DEFER, C.byref(h)))
+        return ParsedScene(h)
     _check(lib().rt_load_gltf(path.encode(), width, height, spp, C.byref(h)))
     return _take_parsed(h)
 
@@ -361,7 +406,8 @@ class Scene:
     uploaded; items="device": the per-triangle items behind those arrays computed there from
     the description's arrays), flattened arrays resident on the current HIP device."""
 
-    def __init__(self, desc: SceneDesc, build: str = "host", records: str = "host", items: str = "host"):
+    @staticmethod
+    def _build_flags(build: str, records: str, items: str, meshes: str = "host") -> int:
         if build not in ("host", "device"):
             raise ValueError(f"build must be 'host' or 'device', not {build!r}")
         if records not in ("host", "device"):
@@ -372,14 +418,35 @@ class Scene:
             raise ValueError(f"items must be 'host' or 'device', not {items!r}")
         if items == "device" and records != "device":
             raise ValueError("items='device' needs build='device' and records='device'")
+        if meshes not in ("host", "device"):
+            raise ValueError(f"meshes must be 'host' or 'device', not {meshes!r}")
+        if meshes == "device" and items != "device":
+            raise ValueError("meshes='device' needs build='device', records='device' and items='device'")
+        return ((RT_BUILD_DEVICE if build == "device" else 0) | (RT_BUILD_DEVICE_RECORDS if records == "device" else 0) |
+                (RT_BUILD_DEVICE_ITEMS if items == "device" else 0) | (RT_BUILD_DEVICE_MESHES if meshes == "device" else 0))
+
+    def __init__(self, desc: SceneDesc, build: str = "host", records: str = "host", items: str = "host"):
+        flags = self._build_flags(build, records, items)
         self.desc = desc
         d, keep = desc.to_c()
         h = C.c_void_p()
-        flags = ((RT_BUILD_DEVICE if build == "device" else 0) | (RT_BUILD_DEVICE_RECORDS if records == "device" else 0) |
-                 (RT_BUILD_DEVICE_ITEMS if items == "device" else 0))
         _check(lib().rt_scene_create_ex(C.byref(d), flags, C.byref(h)))
         self._h = h
         del keep
+
+    @classmethod
+    def from_parsed(cls, parsed: "ParsedScene", build: str = "host", records: str = "host", items: str = "host",
+                    meshes: str = "host") -> "Scene":
+        """rt_scene_create_parsed: the scene of a deferred glTF parse.  meshes="device" (with
+        the other three) flattens the meshes on the device from the buffers' bytes; the
+        description is then made only for what falls back to the host."""
+        flags = cls._build_flags(build, records, items, meshes)
+        h = C.c_void_p()
+        _check(lib().rt_scene_create_parsed(parsed.handle, flags, C.byref(h)))
+        self = cls.__new__(cls)
+        self.desc = None
+        self._h = h
+        return self
 
     def close(self):
         if getattr(self, "_h", None):

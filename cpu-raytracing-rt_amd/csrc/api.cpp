@@ -541,6 +541,8 @@ struct DevBuf {  // RAII device buffer for per-call scratch
 
 }  // namespace
 
+static int check_build_flags(uint32_t build_flags);
+
 extern "C" {
 
 const char* rt_last_error(void) { return g_last_error.c_str(); }
@@ -554,19 +556,49 @@ int rt_device_count(void) {
 int rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out) {
     if (!desc || !out) return set_error(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
-    if (build_flags & ~(RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS | RT_BUILD_DEVICE_ITEMS))
-        return set_error(RT_ERR_INVALID, "unknown build flag");
-    if ((build_flags & RT_BUILD_DEVICE_ITEMS) && !(build_flags & RT_BUILD_DEVICE_RECORDS))
-        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_ITEMS needs RT_BUILD_DEVICE_RECORDS (the items feed the device's record emission)");
-    if ((build_flags & RT_BUILD_DEVICE_RECORDS) && !(build_flags & RT_BUILD_DEVICE))
-        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_RECORDS needs RT_BUILD_DEVICE (the records come from the device's tree)");
+    if (build_flags & RT_BUILD_DEVICE_MESHES)
+        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_MESHES needs a deferred glTF parse (rt_scene_create_parsed): a description has no meshes");
+    if (const int rc = check_build_flags(build_flags)) return rc;
     HostScene hs;
     const int rc = rt::scene_build_host(*desc, hs, build_flags);
     return rc ? rc : rt::scene_upload(hs, out, false);
 }
 int rt_scene_create(const rt_scene_desc* desc, rt_scene** out) { return rt_scene_create_ex(desc, 0, out); }
 
+int rt_scene_create_parsed(rt_parsed_scene* ps, uint32_t build_flags, rt_scene** out) {
+    if (!ps || !out) return set_error(RT_ERR_INVALID, "parsed scene/out is NULL");
+    *out = nullptr;
+    const uint32_t three = RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS | RT_BUILD_DEVICE_ITEMS;
+    if ((build_flags & RT_BUILD_DEVICE_MESHES) && (build_flags & three) != three)
+        return set_error(RT_ERR_INVALID, std::string("RT_BUILD_DEVICE_MESHES needs ") +
+                                             (!(build_flags & RT_BUILD_DEVICE_ITEMS) ? "RT_BUILD_DEVICE_ITEMS"
+                                              : !(build_flags & RT_BUILD_DEVICE_RECORDS) ? "RT_BUILD_DEVICE_RECORDS"
+                                                                                         : "RT_BUILD_DEVICE") +
+                                             " (the flattened meshes feed the device's items)");
+    if (const int rc = check_build_flags(build_flags & ~RT_BUILD_DEVICE_MESHES)) return rc;
+    HostScene hs;
+    int rc;
+    if ((build_flags & RT_BUILD_DEVICE_MESHES) && ps->deferred) {
+        rc = rt::scene_build_parsed(*ps, hs, build_flags);
+    } else {
+        rt_scene_desc desc;
+        if ((rc = rt_parsed_scene_get(ps, &desc, nullptr))) return rc;
+        rc = rt::scene_build_host(desc, hs, build_flags & ~RT_BUILD_DEVICE_MESHES);
+    }
+    return rc ? rc : rt::scene_upload(hs, out, false);
+}
+
 }  // extern "C"
+
+static int check_build_flags(uint32_t build_flags) {
+    if (build_flags & ~(RT_BUILD_DEVICE | RT_BUILD_DEVICE_RECORDS | RT_BUILD_DEVICE_ITEMS))
+        return set_error(RT_ERR_INVALID, "unknown build flag");
+    if ((build_flags & RT_BUILD_DEVICE_ITEMS) && !(build_flags & RT_BUILD_DEVICE_RECORDS))
+        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_ITEMS needs RT_BUILD_DEVICE_RECORDS (the items feed the device's record emission)");
+    if ((build_flags & RT_BUILD_DEVICE_RECORDS) && !(build_flags & RT_BUILD_DEVICE))
+        return set_error(RT_ERR_INVALID, "RT_BUILD_DEVICE_RECORDS needs RT_BUILD_DEVICE (the records come from the device's tree)");
+    return RT_OK;
+}
 
 namespace rt {
 
@@ -582,17 +614,43 @@ static int tri_items_device(const rt_scene_desc& desc, HostBvhArrays& tris, Host
     return emit_tri_bvhs_device_items(desc, 0, tris, ltris, res, err);
 }
 
-int scene_build_host(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags) {
+// The mesh stage of a deferred glTF parse (gltf_items.hip) and the host flatten behind it
+struct ParsedCtx { const rt_parsed_scene* ps; int rc; };
+static int tri_meshes_device(void* ctx, HostBvhArrays& tris, HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err) {
+    return emit_tri_bvhs_device_meshes(*((ParsedCtx*)ctx)->ps, 0, tris, ltris, res, err);
+}
+static bool parsed_arrays(void* ctx, rt_scene_desc& desc, std::string& err) {
+    ParsedCtx& c = *(ParsedCtx*)ctx;
+    if ((c.rc = rt_parsed_scene_get(c.ps, &desc, nullptr))) err = rt_last_error();  // the eager load's code and message
+    return c.rc == RT_OK;
+}
+
+static int scene_build_any(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags, ParsedCtx* parsed) {
     int ndev = 0;
     if ((build_flags & RT_BUILD_DEVICE) && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0))
         return set_error(RT_ERR_DEVICE, "no HIP device visible (RT_BUILD_DEVICE builds on one)");
+    const TriMeshStage stage = {parsed, tri_meshes_device, parsed_arrays};
     std::string err = build_scene(desc, hs, (build_flags & RT_BUILD_DEVICE) ? tri_build_device : nullptr,
                                   (build_flags & RT_BUILD_DEVICE_RECORDS) ? tri_emit_device : nullptr,
-                                  (build_flags & RT_BUILD_DEVICE_ITEMS) ? tri_items_device : nullptr);
-    if (!err.empty()) return set_error(RT_ERR_INVALID, err);
+                                  (build_flags & RT_BUILD_DEVICE_ITEMS) ? tri_items_device : nullptr,
+                                  parsed ? &stage : nullptr);
+    if (!err.empty()) return parsed && parsed->rc ? set_error(parsed->rc, err) : set_error(RT_ERR_INVALID, err);
     for (int k = 0; k < 6; ++k)  // traversal stack words carry node indices in 30 bits (render.hip child_word)
         if (hs.bvh[k].n_nodes() >= (1u << 30)) return set_error(RT_ERR_INVALID, "BVH exceeds 2^30 nodes");
     return RT_OK;
+}
+int scene_build_host(const rt_scene_desc& desc, HostScene& hs, uint32_t build_flags) {
+    return scene_build_any(desc, hs, build_flags, nullptr);
+}
+int scene_build_parsed(const rt_parsed_scene& ps, HostScene& hs, uint32_t build_flags) {
+    rt_scene_desc head;  // the description without its triangle arrays
+    std::memset(&head, 0, sizeof(head));
+    head.n_materials = (uint32_t)ps.mats.size();
+    head.materials = ps.mats.data();
+    head.n_triangles = ps.n_plan_tris;
+    head.tri_mode = ps.tri_mode;
+    ParsedCtx ctx = {&ps, RT_OK};
+    return scene_build_any(head, hs, build_flags, &ctx);
 }
 
 // Scene::new's device side: the flattened scene on the CURRENT HIP device.
@@ -682,7 +740,8 @@ int scene_upload(const HostScene& hs, rt_scene** out, bool replica) {
     s->info.layout_flags = (d.tris.cnodes ? RT_LAYOUT_COMPACT_TRIS : 0u) | (d.lq_boxes ? RT_LAYOUT_LQ_SKIP : 0u) |
                            (d.tris.pnodes ? RT_LAYOUT_PAIR_NODES : 0u) | (hs.device_built ? RT_LAYOUT_DEVICE_BUILT : 0u) |
                            (hs.device_records ? RT_LAYOUT_DEVICE_RECORDS : 0u) |
-                           (hs.device_items ? RT_LAYOUT_DEVICE_ITEMS : 0u);
+                           (hs.device_items ? RT_LAYOUT_DEVICE_ITEMS : 0u) |
+                           (hs.device_meshes ? RT_LAYOUT_DEVICE_MESHES : 0u);
     s->info.build_ms = hs.build_ms;
     s->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = owner.release();

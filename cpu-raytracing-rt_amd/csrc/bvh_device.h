@@ -62,6 +62,25 @@ int build_bvh_device_tree(Arena& m, const double* d_boxes, uint32_t n, uint32_t 
 int emit_tri_bvh_device_core(Arena& m, const TriItem* d_items, double* d_boxes, uint32_t n, bool compact,
                              uint32_t max_levels, HostBvhArrays& out, std::string& err);
 
+// What the item kernels (tri_items.hip ti_items, gltf_items.hip gf_items and gf_scan) leave
+// for the host: the triangles queued for the NaN fix-up, the light triangles, and
+// gf_scan's findings (kScanNonFinite | kScanIndexRange; 0 from ti_items).
+struct ItemsHeader { uint32_t n_nan, n_light, scan; };
+enum : uint32_t { kScanNonFinite = 1u, kScanIndexRange = 2u };
+// tri_items.hip: clears the header (a kernel on `st`; launch before the item kernel).
+void items_header_clear(ItemsHeader* d_hdr, hipStream_t st);
+// tri_items.hip: the tail that both item front ends share, called with the item kernel
+// launched on stream 0 and all of it in the caller's arena: d_items / d_boxes the n items,
+// d_mat the material of each, d_light a byte per material (is_light), d_queue the fix-up
+// queue (kFixCap words), d_hdr the header.  Counts and compacts the light triangles,
+// releases `inputs` once the item kernel is through, patches in the queued items as
+// item_of(ctx, j, item) computes them on the host, and emits both triangle BVHs.  Returns
+// and fills res as a TriBvhItems does; a non-zero header.scan is kDeviceBuildFallback.
+int finish_device_items(Arena& m, uint32_t n, TriItem* d_items, double* d_boxes, uint32_t* d_mat, uint8_t* d_light,
+                        uint32_t* d_queue, ItemsHeader* d_hdr, void* const* inputs, uint32_t n_inputs,
+                        void (*item_of)(const void* ctx, uint32_t j, TriItem& it), const void* ctx, uint32_t max_levels,
+                        HostBvhArrays& tris, HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err);
+
 }  // namespace rt
 
 // -DRT_EMIT_TIMES (a variant build): the wall time of each phase of an emission on stderr

@@ -13,6 +13,7 @@
 // Matrix arithmetic follows cgmath 0.18 (Matrix4 * Matrix4 / Vector4 as
 // column combinations, quaternion -> matrix) so vertices match the
 // reference bit for bit.  Every reference panic becomes an error code.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -23,8 +24,10 @@
 
 #include "../../include/rt_api.h"
 #include "api_internal.h"
+#include "gltf_math.h"
 #include "json.h"
 #include "rt_math.h"
+#include "tri_items.h"
 
 using namespace rt;
 
@@ -110,10 +113,6 @@ M4 mul4(const M4& L, const M4& R) {  // from_cols(a*rhs[c][0] + b*rhs[c][1] + c*
             o.m[c][r] = ((L.m[0][r] * R.m[c][0] + L.m[1][r] * R.m[c][1]) + L.m[2][r] * R.m[c][2]) + L.m[3][r] * R.m[c][3];
     return o;
 }
-void mul4v(const M4& M, const double v[4], double out[4]) {  // m[0]*v0 + m[1]*v1 + m[2]*v2 + m[3]*v3
-    for (int r = 0; r < 4; ++r)
-        out[r] = ((M.m[0][r] * v[0] + M.m[1][r] * v[1]) + M.m[2][r] * v[2]) + M.m[3][r] * v[3];
-}
 M4 from_quat(double s, double x, double y, double z) {  // impl From<Quaternion> for Matrix4
     const double x2 = x + x, y2 = y + y, z2 = z + z;
     const double xx2 = x2 * x, xy2 = x2 * y, xz2 = x2 * z;
@@ -195,6 +194,9 @@ struct Ctx {
     std::vector<Node> nodes;
     rt_parsed_scene* ps;
     Err e;
+    // RT_GLTF_DEFER: convert_primitive records a draw (plan_primitive) instead of triangles
+    bool plan = false;
+    std::map<std::string, uint32_t> plan_bufs;  // uri -> index in ps->bufs, in order of first use
 };
 
 bool bytes_of(Ctx& c, const Accessor& a, const std::string*& bytes, uint64_t& offset, uint64_t& stride,
@@ -213,7 +215,57 @@ float f32_at(const std::string& b, uint64_t pos) {
     return f;
 }
 
+// The three readers' loops over an accessor already resolved to (bytes, offset, stride,
+// count): the eager load and the flatten over a deferred parse's draw plan both run these.
 // read_vertices (scene_builder.rs:269-297)
+bool flatten_positions(const std::string& b, uint64_t off, uint64_t stride, uint64_t count, const double* m,
+                       std::vector<V3>& out, Err& e) {
+    for (uint64_t k = 0; k < count; ++k, off += stride) {
+        if (off + 12 > b.size()) return e.set(RT_ERR_PARSE, "vertex read past end of buffer");
+        const float x = f32_at(b, off), y = f32_at(b, off + 4), z = f32_at(b, off + 8);
+        if (!(gltf_row(m, 3, (double)x, (double)y, (double)z) == 1.0))
+            return e.set(RT_ERR_UNSUPPORTED, "non-affine node transform (pos.w != 1)");
+        out.push_back(gltf_point(m, x, y, z));
+    }
+    return true;
+}
+// read_normals (scene_builder.rs:299-327)
+bool flatten_normals(const std::string& b, uint64_t off, uint64_t stride, uint64_t count, const double* rs,
+                     std::vector<V3>& out, Err& e) {
+    for (uint64_t k = 0; k < count; ++k, off += stride) {
+        if (off + 12 > b.size()) return e.set(RT_ERR_PARSE, "normal read past end of buffer");
+        out.push_back(gltf_normal(rs, f32_at(b, off), f32_at(b, off + 4), f32_at(b, off + 8)));
+    }
+    return true;
+}
+// read_indices (scene_builder.rs:237-267)
+bool flatten_indices(const std::string& b, uint64_t off, uint64_t stride, uint64_t count, uint64_t es,
+                     std::vector<uint32_t>& out, Err& e) {
+    out.reserve(count);
+    for (uint64_t k = 0; k < count; ++k, off += stride) {
+        if (off + es > b.size()) return e.set(RT_ERR_PARSE, "index read past end of buffer");
+        if (es == 2) { uint16_t v; std::memcpy(&v, b.data() + off, 2); out.push_back(v); }
+        else { uint32_t v; std::memcpy(&v, b.data() + off, 4); out.push_back(v); }
+    }
+    return true;
+}
+// make_triangles[_by_indices] (scene_builder.rs:329-356)
+bool gather_triangles(const std::vector<V3>& verts, const std::vector<V3>& norms, const std::vector<uint32_t>& idx,
+                      bool has_idx, uint32_t mid, rt_parsed_scene& ps, Err& e) {
+    const uint64_t n = has_idx ? idx.size() : verts.size();
+    for (uint64_t k = 0; k < n; k += 3) {
+        uint64_t ia = has_idx ? idx[k] : k, ib = has_idx ? idx[k + 1] : k + 1, ic = has_idx ? idx[k + 2] : k + 2;
+        if (ia >= verts.size() || ib >= verts.size() || ic >= verts.size()) return e.set(RT_ERR_PARSE, "index out of range");
+        const V3 vv[3] = {verts[ia], verts[ib], verts[ic]}, nn[3] = {norms[ia], norms[ib], norms[ic]};
+        for (int q = 0; q < 3; ++q) {
+            ps.tri_v.insert(ps.tri_v.end(), {vv[q].x, vv[q].y, vv[q].z});
+            ps.tri_n.insert(ps.tri_n.end(), {nn[q].x, nn[q].y, nn[q].z});
+        }
+        ps.tri_mat.push_back(mid);
+    }
+    return true;
+}
+
 bool read_vertices(Ctx& c, uint64_t ai, const M4& trs, std::vector<V3>& out) {
     if (ai >= c.acc.size()) return c.e.set(RT_ERR_PARSE, "accessor index out of range");
     const Accessor& a = c.acc[ai];
@@ -222,17 +274,8 @@ bool read_vertices(Ctx& c, uint64_t ai, const M4& trs, std::vector<V3>& out) {
     if (a.component_type != 5126 || a.type != "VEC3") return c.e.set(RT_ERR_UNSUPPORTED, "POSITION must be FLOAT VEC3");
     const std::string* b; uint64_t off, stride;
     if (!bytes_of(c, a, b, off, stride, 12)) return false;
-    for (uint64_t k = 0; k < a.count; ++k, off += stride) {
-        if (off + 12 > b->size()) return c.e.set(RT_ERR_PARSE, "vertex read past end of buffer");
-        double v[4] = {(double)f32_at(*b, off), (double)f32_at(*b, off + 4), (double)f32_at(*b, off + 8), 1.0};
-        double p[4];
-        mul4v(trs, v, p);
-        if (!(p[3] == 1.0)) return c.e.set(RT_ERR_UNSUPPORTED, "non-affine node transform (pos.w != 1)");
-        out.push_back(v3(p[0], p[1], p[2]));
-    }
-    return true;
+    return flatten_positions(*b, off, stride, a.count, &trs.m[0][0], out, c.e);
 }
-// read_normals (scene_builder.rs:299-327)
 bool read_normals(Ctx& c, uint64_t ai, const M4& trs, std::vector<V3>& out) {
     if (ai >= c.acc.size()) return c.e.set(RT_ERR_PARSE, "accessor index out of range");
     const Accessor& a = c.acc[ai];
@@ -243,16 +286,8 @@ bool read_normals(Ctx& c, uint64_t ai, const M4& trs, std::vector<V3>& out) {
     if (!bytes_of(c, a, b, off, stride, 12)) return false;
     double rs[3][3];
     cof3(trs, rs);
-    for (uint64_t k = 0; k < a.count; ++k, off += stride) {
-        if (off + 12 > b->size()) return c.e.set(RT_ERR_PARSE, "normal read past end of buffer");
-        double x = (double)f32_at(*b, off), y = (double)f32_at(*b, off + 4), z = (double)f32_at(*b, off + 8);
-        V3 n = v3((rs[0][0] * x + rs[1][0] * y) + rs[2][0] * z, (rs[0][1] * x + rs[1][1] * y) + rs[2][1] * z,
-                  (rs[0][2] * x + rs[1][2] * y) + rs[2][2] * z);
-        out.push_back(normalize(n));
-    }
-    return true;
+    return flatten_normals(*b, off, stride, a.count, &rs[0][0], out, c.e);
 }
-// read_indices (scene_builder.rs:237-267)
 bool read_indices(Ctx& c, uint64_t ai, std::vector<uint32_t>& out) {
     if (ai >= c.acc.size()) return c.e.set(RT_ERR_PARSE, "accessor index out of range");
     const Accessor& a = c.acc[ai];
@@ -264,13 +299,7 @@ bool read_indices(Ctx& c, uint64_t ai, std::vector<uint32_t>& out) {
     const uint64_t es = a.component_type == 5123 ? 2 : 4;
     const std::string* b; uint64_t off, stride;
     if (!bytes_of(c, a, b, off, stride, es)) return false;
-    out.reserve(a.count);
-    for (uint64_t k = 0; k < a.count; ++k, off += stride) {
-        if (off + es > b->size()) return c.e.set(RT_ERR_PARSE, "index read past end of buffer");
-        if (es == 2) { uint16_t v; std::memcpy(&v, b->data() + off, 2); out.push_back(v); }
-        else { uint32_t v; std::memcpy(&v, b->data() + off, 4); out.push_back(v); }
-    }
-    return true;
+    return flatten_indices(*b, off, stride, a.count, es, out, c.e);
 }
 
 // make_metadata (scene_builder.rs:227-235) with the serde defaults of parser.rs
@@ -310,8 +339,86 @@ bool make_material(Ctx& c, const Json* m, rt_material& out) {
     return true;
 }
 
+// ---- the draw plan of a deferred parse (RT_GLTF_DEFER) ----------------------
+// Planning returns false, with or without an error set, wherever the eager load would
+// report an error or the device flatten has no answer; rt_load_gltf_ex then runs the eager
+// load, so the error reported is always the eager path's.
+struct PlanAcc { uint32_t buf; uint64_t off, stride, count; };
+bool plan_accessor(Ctx& c, uint64_t ai, bool index, uint64_t& width, PlanAcc& out) {
+    if (ai >= c.acc.size()) return false;
+    const Accessor& a = c.acc[ai];
+    if (!a.has_view) return false;
+    uint64_t es = 4;  // component size
+    if (index) {
+        if ((a.component_type != 5123 && a.component_type != 5125) || a.type != "SCALAR") return false;
+        es = width = a.component_type == 5123 ? 2 : 4;
+    } else {
+        if (a.component_type != 5126 || a.type != "VEC3") return false;
+        width = 12;
+    }
+    const std::string* b; uint64_t off, stride;
+    if (!bytes_of(c, a, b, off, stride, width)) return false;
+    if (off % es || stride % es || stride == 0 || stride > 0xffffffffull || a.count > 0xffffffffull) return false;
+    if (a.count && (unsigned __int128)off + (unsigned __int128)(a.count - 1) * stride + width > b->size())
+        return false;  // the last element ends past the buffer
+    const std::string& uri = c.buffer_uri[c.views[a.view].buffer];
+    auto at = c.plan_bufs.find(uri);
+    if (at == c.plan_bufs.end()) at = c.plan_bufs.emplace(uri, (uint32_t)c.plan_bufs.size()).first;
+    out = PlanAcc{at->second, off, stride, a.count};
+    return true;
+}
+bool plan_primitive(Ctx& c, const Json& p, const M4& trs) {
+    uint64_t mode;
+    if (!get_uint(p, "mode", false, 4, mode, c.e) || mode != 4) return false;
+    const Json* attr = p.get("attributes");
+    if (!attr) return false;
+    uint64_t pos_i, nrm_i, idx_i = 0, mat_i = 0, w;
+    bool has_n, has_idx, has_mat;
+    if (!get_uint(*attr, "POSITION", true, 0, pos_i, c.e) || !get_opt_uint(*attr, "NORMAL", has_n, nrm_i, c.e) || !has_n)
+        return false;
+    if (!get_opt_uint(p, "indices", has_idx, idx_i, c.e) || !get_opt_uint(p, "material", has_mat, mat_i, c.e)) return false;
+    PlanAcc pos, nrm, idx{0, 0, 0, 0};
+    if (!plan_accessor(c, pos_i, false, w, pos) || !plan_accessor(c, nrm_i, false, w, nrm) || pos.count != nrm.count)
+        return false;
+    uint64_t iw = 0;
+    if (has_idx && !plan_accessor(c, idx_i, true, iw, idx)) return false;
+    const uint64_t corners = has_idx ? idx.count : pos.count;
+    if (corners % 3) return false;
+    // row 3 (+-0, +-0, +-0, 1): pos.w == 1.0 exactly where the vertex is finite
+    if (!(trs.m[0][3] == 0.0 && trs.m[1][3] == 0.0 && trs.m[2][3] == 0.0 && trs.m[3][3] == 1.0)) return false;
+    const Json* mats = c.root->get("materials");
+    const Json* mj = nullptr;
+    if (has_mat) {
+        if (!mats || mats->kind != Json::Array || mat_i >= mats->arr.size()) return false;
+        mj = &mats->arr[mat_i];
+    }
+    rt_material m;
+    if (!make_material(c, mj, m)) return false;
+    rt_parsed_scene& ps = *c.ps;
+    if (ps.n_plan_tris + corners / 3 > (1ull << 30)) return false;
+    GltfDraw d;
+    std::memset(&d, 0, sizeof(d));
+    std::memcpy(d.m, &trs.m[0][0], sizeof(d.m));
+    double rs[3][3];
+    cof3(trs, rs);
+    std::memcpy(d.cof, &rs[0][0], sizeof(d.cof));
+    d.pos_off = pos.off; d.pos_stride = (uint32_t)pos.stride; d.pos_buf = pos.buf;
+    d.nrm_off = nrm.off; d.nrm_stride = (uint32_t)nrm.stride; d.nrm_buf = nrm.buf;
+    d.idx_off = idx.off; d.idx_stride = (uint32_t)idx.stride; d.idx_buf = idx.buf; d.idx_width = (uint32_t)iw;
+    d.n_verts = (uint32_t)pos.count;
+    d.n_idx = (uint32_t)idx.count;
+    d.n_tris = (uint32_t)(corners / 3);
+    d.first_tri = (uint32_t)ps.n_plan_tris;
+    d.mid = (uint32_t)ps.mats.size();
+    ps.mats.push_back(m);
+    ps.draws.push_back(d);
+    ps.n_plan_tris += d.n_tris;
+    return true;
+}
+
 // convert_primitive (scene_builder.rs:209-225) + make_triangles[_by_indices] (:329-356)
 bool convert_primitive(Ctx& c, const Json& p, const M4& trs) {
+    if (c.plan) return plan_primitive(c, p, trs);
     uint64_t mode;
     if (!get_uint(p, "mode", false, 4, mode, c.e)) return false;
     if (mode != 4) return c.e.set(RT_ERR_UNSUPPORTED, "supported only triangles for primitive.mode");
@@ -343,18 +450,7 @@ bool convert_primitive(Ctx& c, const Json& p, const M4& trs) {
     if (!make_material(c, mj, m)) return false;
     const uint32_t mid = (uint32_t)c.ps->mats.size();
     c.ps->mats.push_back(m);
-    const uint64_t n = has_idx ? idx.size() : verts.size();
-    for (uint64_t k = 0; k < n; k += 3) {
-        uint64_t ia = has_idx ? idx[k] : k, ib = has_idx ? idx[k + 1] : k + 1, ic = has_idx ? idx[k + 2] : k + 2;
-        if (ia >= verts.size() || ib >= verts.size() || ic >= verts.size()) return c.e.set(RT_ERR_PARSE, "index out of range");
-        const V3 vv[3] = {verts[ia], verts[ib], verts[ic]}, nn[3] = {norms[ia], norms[ib], norms[ic]};
-        for (int q = 0; q < 3; ++q) {
-            c.ps->tri_v.insert(c.ps->tri_v.end(), {vv[q].x, vv[q].y, vv[q].z});
-            c.ps->tri_n.insert(c.ps->tri_n.end(), {nn[q].x, nn[q].y, nn[q].z});
-        }
-        c.ps->tri_mat.push_back(mid);
-    }
-    return true;
+    return gather_triangles(verts, norms, idx, has_idx, mid, *c.ps, c.e);
 }
 
 bool convert_node(Ctx& c, uint64_t ni, int depth) {  // :190-207
@@ -518,9 +614,66 @@ bool load(Ctx& c, const std::string& path, uint32_t W, uint32_t H, uint32_t spp)
 
 }  // namespace
 
-extern "C" int rt_load_gltf(const char* path, uint32_t W, uint32_t H, uint32_t spp, rt_parsed_scene** out) {
+namespace rt {
+
+int parsed_materialise(const rt_parsed_scene* cps) {
+    rt_parsed_scene& ps = *const_cast<rt_parsed_scene*>(cps);  // parse results are never const objects
+    if (!ps.deferred || ps.flat > 0) return RT_OK;
+    if (ps.flat < 0) return set_error(ps.flat_rc, ps.flat_msg);
+    Err e;
+    ps.tri_v.reserve(ps.n_plan_tris * 9);
+    ps.tri_n.reserve(ps.n_plan_tris * 9);
+    ps.tri_mat.reserve(ps.n_plan_tris);
+    std::vector<V3> verts, norms;
+    std::vector<uint32_t> idx;
+    for (const GltfDraw& d : ps.draws) {  // convert_primitive's order: vertices, normals, indices, triangles
+        verts.clear(); norms.clear(); idx.clear();
+        if (!flatten_positions(ps.bufs[d.pos_buf], d.pos_off, d.pos_stride, d.n_verts, d.m, verts, e) ||
+            !flatten_normals(ps.bufs[d.nrm_buf], d.nrm_off, d.nrm_stride, d.n_verts, d.cof, norms, e) ||
+            (d.idx_width && !flatten_indices(ps.bufs[d.idx_buf], d.idx_off, d.idx_stride, d.n_idx, d.idx_width, idx, e)) ||
+            !gather_triangles(verts, norms, idx, d.idx_width != 0, d.mid, ps, e))
+            break;
+    }
+    if (e.code != RT_OK) {
+        ps.tri_v = {}; ps.tri_n = {}; ps.tri_mat = {};
+        ps.flat = -1; ps.flat_rc = e.code; ps.flat_msg = e.msg;
+        return set_error(e.code, e.msg);
+    }
+    ps.flat = 1;
+    return RT_OK;
+}
+
+void gltf_item_of(const rt_parsed_scene& ps, uint32_t j, TriItem& it) {
+    // the last draw that starts at or before j (a draw without triangles never is)
+    auto at = std::upper_bound(ps.draws.begin(), ps.draws.end(), j,
+                               [](uint32_t v, const GltfDraw& d) { return v < d.first_tri; });
+    const GltfDraw& d = *(at - 1);
+    V3 p[3], n[3];
+    for (uint32_t q = 0; q < 3; ++q) {
+        uint64_t v = (uint64_t)(j - d.first_tri) * 3 + q;
+        if (d.idx_width) {
+            const char* at_i = ps.bufs[d.idx_buf].data() + d.idx_off + v * d.idx_stride;
+            if (d.idx_width == 2) { uint16_t x; std::memcpy(&x, at_i, 2); v = x; }
+            else { uint32_t x; std::memcpy(&x, at_i, 4); v = x; }
+        }
+        const std::string& pb = ps.bufs[d.pos_buf];
+        const std::string& nb = ps.bufs[d.nrm_buf];
+        const uint64_t po = d.pos_off + v * d.pos_stride, no = d.nrm_off + v * d.nrm_stride;
+        p[q] = gltf_point(d.m, f32_at(pb, po), f32_at(pb, po + 4), f32_at(pb, po + 8));
+        n[q] = gltf_normal(d.cof, f32_at(nb, no), f32_at(nb, no + 4), f32_at(nb, no + 8));
+    }
+    tri_item_gltf(p[0], p[1], p[2], n[0], n[1], n[2], it);
+    it.mat = d.mid;
+    it.gid = (int32_t)j;
+}
+
+}  // namespace rt
+
+extern "C" int rt_load_gltf_ex(const char* path, uint32_t W, uint32_t H, uint32_t spp, uint32_t flags,
+                               rt_parsed_scene** out) {
     if (!path || !out) return set_error(RT_ERR_INVALID, "path/out is NULL");
     *out = nullptr;
+    if (flags & ~RT_GLTF_DEFER) return set_error(RT_ERR_INVALID, "unknown load flag");
     if (W == 0 || H == 0 || spp == 0) return set_error(RT_ERR_INVALID, "width/height/spp must be > 0");
     std::ifstream f(path, std::ios::binary);
     if (!f) return set_error(RT_ERR_IO, std::string("Couldn't find or load gltf file: ") + path);
@@ -529,15 +682,38 @@ extern "C" int rt_load_gltf(const char* path, uint32_t W, uint32_t H, uint32_t s
     Json root;
     std::string err = json_parse(ss.str(), root);
     if (!err.empty()) return set_error(RT_ERR_PARSE, "can't parse glTF: " + err);
+    std::map<std::string, std::string> buffers;  // what a plan that gave up has read already
+    if (flags & RT_GLTF_DEFER) {
+        rt_parsed_scene* ps = new rt_parsed_scene();
+        ps->tri_mode = RT_TRI_GLTF;
+        ps->deferred = true;
+        Ctx c;
+        c.root = &root;
+        c.ps = ps;
+        c.plan = true;
+        if (load(c, path, W, H, spp)) {
+            ps->bufs.resize(c.plan_bufs.size());
+            for (const auto& b : c.plan_bufs) ps->bufs[b.second] = std::move(c.buffers[b.first]);
+            *out = ps;
+            return RT_OK;
+        }
+        delete ps;
+        buffers = std::move(c.buffers);
+    }
     rt_parsed_scene* ps = new rt_parsed_scene();
     ps->tri_mode = RT_TRI_GLTF;
     Ctx c;
     c.root = &root;
     c.ps = ps;
+    c.buffers = std::move(buffers);
     if (!load(c, path, W, H, spp)) {
         delete ps;
         return set_error(c.e.code, c.e.msg);
     }
     *out = ps;
     return RT_OK;
+}
+
+extern "C" int rt_load_gltf(const char* path, uint32_t W, uint32_t H, uint32_t spp, rt_parsed_scene** out) {
+    return rt_load_gltf_ex(path, W, H, spp, 0, out);
 }

@@ -225,6 +225,7 @@ extern "C" int rt_parse_custom_scene(const char* text, rt_parsed_scene** out) {
 extern "C" int rt_parsed_scene_get(const rt_parsed_scene* ps, rt_scene_desc* d, rt_render_params* p) {
     if (!ps) return set_error(RT_ERR_INVALID, "parsed scene is NULL");
     if (d) {
+        if (const int rc = parsed_materialise(ps)) return rc;  // a deferred glTF parse: the host flatten, once
         std::memset(d, 0, sizeof(*d));
         d->n_materials = (uint32_t)ps->mats.size();
         d->materials = ps->mats.data();

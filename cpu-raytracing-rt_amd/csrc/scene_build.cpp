@@ -514,13 +514,15 @@ HostBvh build_bvh(const std::vector<Box3>& boxes) {
     return h;
 }
 
-std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_build, TriBvhEmit tri_emit,
-                        TriBvhItems tri_items) {
+std::string build_scene(const rt_scene_desc& desc, HostScene& out, TriBvhBuild tri_build, TriBvhEmit tri_emit,
+                        TriBvhItems tri_items, const TriMeshStage* tri_meshes) {
     auto t0 = std::chrono::steady_clock::now();
+    rt_scene_desc d = desc;  // with tri_meshes the triangle arrays arrive when the host first needs them
+    bool have_arrays = !tri_meshes;
     if (d.n_materials == 0 && (d.n_shapes > 0 || d.n_triangles > 0)) return "scene has primitives but no materials";
     if (d.n_shapes > 0 && !d.shapes) return "shapes is NULL";
-    if (d.n_triangles > 0 && (!d.tri_vertices || !d.tri_material)) return "triangle arrays are NULL";
-    if (d.n_triangles > 0 && d.tri_mode == RT_TRI_GLTF && !d.tri_normals) return "glTF triangles need normals";
+    if (have_arrays && d.n_triangles > 0 && (!d.tri_vertices || !d.tri_material)) return "triangle arrays are NULL";
+    if (have_arrays && d.n_triangles > 0 && d.tri_mode == RT_TRI_GLTF && !d.tri_normals) return "glTF triangles need normals";
     if ((uint64_t)d.n_shapes + d.n_triangles > 0x7fffffffull) return "too many primitives for int32 ids";
     out.mats.resize(d.n_materials);
     for (uint32_t i = 0; i < d.n_materials; ++i) {
@@ -574,7 +576,10 @@ std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_
     // The triangle items (tri_items.h): on the host here, or, with tri_items, on the device,
     // and then here only for a triangle BVH that the device path left to the host.
     std::vector<TriItem> tris;
+    std::string arrays_err;
     auto host_items = [&]() -> const char* {
+        if (!have_arrays && !tri_meshes->arrays(tri_meshes->ctx, d, arrays_err)) return arrays_err.c_str();
+        have_arrays = true;
         auto t1 = std::chrono::steady_clock::now();
         tris.resize(d.n_triangles);
         for (uint64_t j = 0; j < d.n_triangles; ++j) {
@@ -589,8 +594,14 @@ std::string build_scene(const rt_scene_desc& d, HostScene& out, TriBvhBuild tri_
         return nullptr;
     };
     TriItemsOutcome dev;
-    const bool on_device = tri_items && d.n_triangles > 0;
-    if (on_device) {
+    const bool on_device = (tri_items || tri_meshes) && d.n_triangles > 0;
+    if (on_device && tri_meshes) {
+        std::string err;
+        if (tri_meshes->run(tri_meshes->ctx, out.bvh[2], out.bvh[5], dev, err) == kDeviceBuildError) return err;
+        for (int made : dev.made)
+            if (made == kDeviceBuildDone)
+                out.device_built = out.device_records = out.device_items = out.device_meshes = true;
+    } else if (on_device) {
         for (uint64_t j = 0; j < d.n_triangles; ++j)
             if (d.tri_material[j] >= d.n_materials) return "triangle material out of range";
         std::string err;

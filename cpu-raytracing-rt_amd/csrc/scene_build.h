@@ -12,6 +12,8 @@
 #include "rt_math.h"
 #include "tri_items.h"
 
+struct rt_parsed_scene;
+
 namespace rt {
 
 // One BVH in host form: pre-order nodes + primitive permutation.
@@ -119,6 +121,7 @@ struct HostScene {
     bool device_built = false;  // a triangle BVH came from build_bvh_device
     bool device_records = false;  // a triangle BVH's arrays came from emit_tri_bvh_device
     bool device_items = false;  // ... emitted from items computed on the device (tri_items.hip)
+    bool device_meshes = false;  // ... from items flattened there from glTF accessor bytes (gltf_items.hip)
 };
 // tri_build: makes the two triangle BVHs and returns as build_bvh_device does (the host
 // builder runs on kDeviceBuildFallback); null: the host builder.  The small shape BVHs
@@ -143,8 +146,23 @@ using TriBvhItems = int (*)(const rt_scene_desc& desc, HostBvhArrays& tris, Host
 // tri_items.hip: the TriBvhItems of the current HIP device.
 int emit_tri_bvhs_device_items(const rt_scene_desc& desc, uint32_t max_levels, HostBvhArrays& tris,
                                HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err);
+// gltf_items.hip: the mesh stage of the current HIP device, for a deferred glTF parse: gf_scan
+// and gf_items go from the buffers' bytes and the draw plan to the items, then tri_items.hip's tail.
+int emit_tri_bvhs_device_meshes(const rt_parsed_scene& ps, uint32_t max_levels, HostBvhArrays& tris,
+                                HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err);
+// tri_meshes: the stage before the items, for a deferred glTF parse.  build_scene is then
+// given the description without its triangle arrays (materials, n_triangles, tri_mode).
+// run flattens the meshes on the device and emits both triangle BVHs from the items, as a
+// TriBvhItems returns.  arrays fills in desc's triangle arrays (the host flatten, made on
+// first use) for whatever the device left to the host; false: err is the flatten's error.
+struct TriMeshStage {
+    void* ctx;
+    int (*run)(void* ctx, HostBvhArrays& tris, HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err);
+    bool (*arrays)(void* ctx, rt_scene_desc& desc, std::string& err);
+};
 // Returns empty string on success, else an error message.
 std::string build_scene(const rt_scene_desc& desc, HostScene& out, TriBvhBuild tri_build = nullptr,
-                        TriBvhEmit tri_emit = nullptr, TriBvhItems tri_items = nullptr);
+                        TriBvhEmit tri_emit = nullptr, TriBvhItems tri_items = nullptr,
+                        const TriMeshStage* tri_meshes = nullptr);
 
 }  // namespace rt

@@ -9,51 +9,32 @@
 //   ti_light_reduce   light triangles per block of kScanTile
 //   ti_light_blocks   one block: exclusive scan of the block sums, the total
 //   ti_compact        the light triangles' items and boxes, stably, into arrays of their own
-// ti_items: a block takes kTile = 64 triangles.  All 256 lanes stage the tile's inputs with
-// 16-byte loads straight into the LDS slots of the items they belong to (vertices, glTF
-// normals and the material are words of the item as they are), wave 0 computes a triangle
-// per lane in its item's slot, and all lanes store the items and the boxes as 16-byte
-// words.  An item takes kStride = 37 eight-byte words of LDS, not 36: with an odd stride
-// the 8-byte accesses of 32 consecutive lanes fall into 32 different bank pairs.
+// ti_items: a block takes a tile of 64 triangles (tri_tile.h, shared with gltf_items.hip's
+// gf_items).  All 256 lanes stage the tile's inputs with 16-byte loads straight into the
+// LDS slots of the items they belong to (vertices, glTF normals and the material are words
+// of the item as they are), wave 0 computes a triangle per lane in its item's slot, and
+// all lanes store the items and the boxes as 16-byte words.
 // Words that are only copied never pass through a floating-point register.
+// finish_device_items is the tail after the item kernel, shared with gltf_items.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "bvh_device.h"
 #include "scene_build.h"
+#include "tri_tile.h"
 
 namespace rt {
 namespace {
 
-constexpr uint32_t kThreads = 256;            // four wave64s
-constexpr uint32_t kWaves = kThreads / 64;
-constexpr uint32_t kTile = 64;                // triangles per block of ti_items: a triangle per lane of wave 0
+using namespace tile;
 constexpr uint32_t kScanTile = 1024;          // triangles per block of the light scan
-constexpr uint32_t kFixCap = 65536;           // fix-up queue: more NaN triangles than this and the host computes all
-constexpr uint64_t kMaxPrims = 1ull << 30;    // as the builder's
 constexpr uint32_t kNone = 0xffffffffu;
-typedef unsigned long long u64;
-
-// TriItem as 36 eight-byte words (bvh_emit.hip asserts the same offsets)
-constexpr uint32_t kItemWords = sizeof(TriItem) / 8, kItemParts = kItemWords / 2;
-constexpr uint32_t kStride = kItemWords + 1;  // LDS words per item: odd
-constexpr uint32_t kWBa = offsetof(TriItem, t.ba) / 8, kWNa = offsetof(TriItem, t.na) / 8,
-                   kWB = offsetof(TriItem, b) / 8, kWMatGid = offsetof(TriItem, mat) / 8,
-                   kWBox = offsetof(TriItem, box) / 8;
-static_assert(offsetof(TriItem, t.a) == 0 && kWBa == 3 && offsetof(TriItem, t.ng) == 72 && kWNa == 13 && kWB == 22 &&
-              offsetof(TriItem, c) == 200 && offsetof(TriItem, mat) == 224 && offsetof(TriItem, gid) == 228 &&
-              kWBox == 29 && kItemWords == 36, "TriItem's words as the kernels index them");
+typedef ItemsHeader Header;
 // custom mode: where a tile's positions and rotations wait in the item's slot (the normals' words)
 constexpr uint32_t kWPos = kWNa, kWRot = kWNa + 3;
 
-struct Header { uint32_t n_nan; uint32_t n_light; };
-
-__global__ void ti_init(Header* h) { h->n_nan = 0; h->n_light = 0; }
-
-__device__ __forceinline__ bool nan_bits(u64 w) { return (w & 0x7fffffffffffffffull) > 0x7ff0000000000000ull; }
-__device__ __forceinline__ double as_f64(u64 w) { return __longlong_as_double((long long)w); }
-__device__ __forceinline__ u64 as_u64(double v) { return (u64)__double_as_longlong(v); }
+__global__ void ti_init(Header* h) { h->n_nan = 0; h->n_light = 0; h->scan = 0; }
 
 // word k of a triangle's nine vertex doubles -> its word in the item (a | b, c)
 __device__ __forceinline__ uint32_t vertex_word(uint32_t k) { return k < 3 ? k : kWB + k - 3; }
@@ -75,9 +56,6 @@ __device__ __forceinline__ void stage(const u64* src, uint32_t cnt, uint32_t fir
         s[w / per * kStride + (vertex ? vertex_word(w % per) : first + w % per)] = src[w];
     }
 }
-
-__device__ __forceinline__ V3 lds3(const u64* p) { return v3(as_f64(p[0]), as_f64(p[1]), as_f64(p[2])); }
-__device__ __forceinline__ void put3(u64* p, V3 v) { p[0] = as_u64(v.x); p[1] = as_u64(v.y); p[2] = as_u64(v.z); }
 
 // items[j] and boxes[j] of triangles j < n.  nrm: glTF mode (normals); else custom mode
 // with pos / rot, either of which may be null (0 / identity).  queue: the triangles with a
@@ -112,13 +90,11 @@ __global__ __launch_bounds__(kThreads) void ti_items(const u64* vtx, const u64* 
         bool bad = false;
         if (tid < cnt) {
             u64* it = s + tid * kStride;
-            const V3 a = lds3(it), b = lds3(it + kWB), c = lds3(it + kWB + 3);
-            TriItem r;
-            if (gltf) {  // a, b, c and the normals stay as staged; the normals take no part in the arithmetic
-                tri_item_gltf(a, b, c, v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0), r);
-                put3(it + kWBa, r.t.ba); put3(it + kWBa + 3, r.t.ca); put3(it + kWBa + 6, r.t.ng);
-                it[kWBa + 9] = as_u64(r.t.inv_area);
+            if (gltf) {
+                gltf_item_in_slot(it);
             } else {
+                const V3 a = lds3(it), b = lds3(it + kWB), c = lds3(it + kWB + 3);
+                TriItem r;
                 const V3 p = pos ? lds3(it + kWPos) : v3(0, 0, 0);
                 const Quat q = rot ? Quat{as_f64(it[kWRot]), lds3(it + kWRot + 1)} : Quat{1.0, v3(0, 0, 0)};
                 for (uint32_t k = 0; k < 9; ++k) bad = bad || nan_bits(it[vertex_word(k)]);
@@ -129,33 +105,17 @@ __global__ __launch_bounds__(kThreads) void ti_items(const u64* vtx, const u64* 
                 it[kWBa + 9] = as_u64(r.t.inv_area);
                 put3(it + kWNa, r.t.na); put3(it + kWNa + 3, r.t.nb); put3(it + kWNa + 6, r.t.nc);
                 put3(it + kWB, r.b); put3(it + kWB + 3, r.c);
+                put3(it + kWBox, r.box.min); put3(it + kWBox + 3, r.box.max);
             }
-            put3(it + kWBox, r.box.min); put3(it + kWBox + 3, r.box.max);
             it[kItemWords - 1] = 0;  // TriItem's tail padding
             s32[(tid * kStride + kWMatGid) * 2 + 1] = n_shapes + j0 + tid;  // gid
             // every double of the item as it stands (in glTF mode these hold all the inputs)
-            for (uint32_t k = 0; k < kItemWords - 1; ++k)
-                if (k != kWMatGid) bad = bad || nan_bits(it[k]);
+            bad = bad || item_has_nan(it);
         }
-        const u64 vote = __ballot(bad);
-        if (vote) {  // one atomic per wave that has any
-            uint32_t base = 0;
-            if (tid == 0) base = atomicAdd(&h->n_nan, (uint32_t)__popcll(vote));
-            base = __shfl(base, 0);
-            const uint32_t at = base + (uint32_t)__popcll(vote & ((1ull << tid) - 1ull));
-            if (bad && at < kFixCap) queue[at] = j0 + tid;
-        }
+        queue_bad(bad, j0 + tid, queue, h);
     }
     __syncthreads();
-
-    for (uint32_t c = tid; c < cnt * kItemParts; c += kThreads) {
-        const u64* w = s + c / kItemParts * kStride + c % kItemParts * 2;
-        items[(size_t)j0 * kItemParts + c] = make_ulonglong2(w[0], w[1]);
-    }
-    for (uint32_t c = tid; c < cnt * 3; c += kThreads) {
-        const u64* w = s + c / 3 * kStride + kWBox + c % 3 * 2;
-        boxes[(size_t)j0 * 3 + c] = make_ulonglong2(w[0], w[1]);
-    }
+    store_tile(s, j0, cnt, items, boxes);
 }
 
 // fix[e] (contiguous, computed by the host) -> items[queue[e]] and its box
@@ -244,15 +204,80 @@ inline uint32_t blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 
 
 }  // namespace
 
-#define TI_TRY(call)                                                                         \
-    do {                                                                                     \
-        const hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) { err = hipGetErrorString(e_); tris.dev.reset(); ltris.dev.reset(); return kDeviceBuildError; } \
-    } while (0)
-#define TI_SCRATCH_OK()                                                                      \
-    do {                                                                                     \
-        if (!m.ok()) { if (m.oom) return kDeviceBuildFallback; TI_TRY(m.err); }              \
-    } while (0)
+void items_header_clear(ItemsHeader* d_hdr, hipStream_t st) { ti_init<<<1, 1, 0, st>>>(d_hdr); }
+
+int finish_device_items(Arena& m, uint32_t n, TriItem* d_items, double* d_boxes, uint32_t* d_mat, uint8_t* d_light,
+                        uint32_t* d_queue, ItemsHeader* d_hdr, void* const* inputs, uint32_t n_inputs,
+                        void (*item_of)(const void* ctx, uint32_t j, TriItem& it), const void* ctx, uint32_t max_levels,
+                        HostBvhArrays& tris, HostBvhArrays& ltris, TriItemsOutcome& res, std::string& err) {
+    const hipStream_t st = 0;
+    RT_EMIT_MARK_START();
+    const uint32_t nblk = blocks(n, kScanTile);
+    uint32_t* d_agg = m.get<uint32_t>(nblk);
+    TI_SCRATCH_OK();
+    ti_light_reduce<<<nblk, kThreads, 0, st>>>(d_mat, d_light, n, d_agg);
+    ti_light_blocks<<<1, kThreads, 0, st>>>(d_agg, nblk, d_hdr);
+    TI_TRY(hipGetLastError());
+    Header h;
+    TI_TRY(hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    TI_TRY(hipStreamSynchronize(st));
+    for (uint32_t k = 0; k < n_inputs; ++k) m.release(inputs[k]);
+    RT_EMIT_MARK("light scan");
+    // the host computes every item, as without this path (and reports what the scan found)
+    if (h.scan || h.n_nan > kFixCap) return kDeviceBuildFallback;
+    res.n_light = h.n_light;
+
+    // NaN bit patterns are not promised to be the host's: those items come from the host
+    if (h.n_nan) {
+        std::vector<uint32_t> idx(h.n_nan);
+        TI_TRY(hipMemcpy(idx.data(), d_queue, (size_t)h.n_nan * 4, hipMemcpyDeviceToHost));
+        std::vector<TriItem> fix(h.n_nan);
+        for (uint32_t e = 0; e < h.n_nan; ++e) item_of(ctx, idx[e], fix[e]);
+        TriItem* d_fix = m.get<TriItem>(h.n_nan);
+        TI_SCRATCH_OK();
+        TI_TRY(hipMemcpyAsync(d_fix, fix.data(), (size_t)h.n_nan * sizeof(TriItem), hipMemcpyHostToDevice, st));
+        ti_patch<<<blocks((uint64_t)h.n_nan * kItemParts, kThreads), kThreads, 0, st>>>(
+            (const ulonglong2*)d_fix, d_queue, h.n_nan, (ulonglong2*)d_items, (u64*)d_boxes);
+        TI_TRY(hipGetLastError());
+        TI_TRY(hipStreamSynchronize(st));  // fix is the copy's source until here
+        m.release(d_fix);
+        RT_EMIT_MARK("fix-up");
+    }
+
+    // bvh[5]'s items: the light triangles, in list order
+    TriItem* d_litems = nullptr;
+    double* d_lboxes = nullptr;
+    if (h.n_light) {
+        d_litems = m.get<TriItem>(h.n_light);
+        d_lboxes = m.get<double>((size_t)h.n_light * 6);
+        if (m.oom) {  // bvh[5] alone takes the host path
+            m.oom = false;
+            m.release(d_litems);
+            d_litems = nullptr;
+        } else {
+            TI_SCRATCH_OK();
+            ti_compact<<<nblk, kThreads, 0, st>>>((const ulonglong2*)d_items, (const ulonglong2*)d_boxes, d_mat, d_light, n,
+                                                  d_agg, (ulonglong2*)d_litems, (ulonglong2*)d_lboxes);
+            TI_TRY(hipGetLastError());
+            TI_TRY(hipStreamSynchronize(st));
+        }
+        RT_EMIT_MARK("light compact");
+    }
+    m.release(d_mat);
+    m.release(d_light);
+    m.release(d_queue);
+    m.release(d_agg);
+
+    // both BVHs from the one item array; the arena frees the items when this returns
+    res.made[0] = emit_tri_bvh_device_core(m, d_items, d_boxes, n, true, max_levels, tris, err);
+    if (res.made[0] == kDeviceBuildError) { ltris.dev.reset(); return kDeviceBuildError; }
+    m.oom = false;  // an allocation the first BVH missed says nothing about the second
+    if (d_litems) res.made[1] = emit_tri_bvh_device_core(m, d_litems, d_lboxes, h.n_light, false, max_levels, ltris, err);
+    if (res.made[1] == kDeviceBuildError) { tris.dev.reset(); return kDeviceBuildError; }
+    return kDeviceBuildDone;
+}
+
+static void desc_item_of(const void* ctx, uint32_t j, TriItem& it) { tri_item_of(*(const rt_scene_desc*)ctx, j, it); }
 
 int emit_tri_bvhs_device_items(const rt_scene_desc& d, uint32_t max_levels, HostBvhArrays& tris, HostBvhArrays& ltris,
                                TriItemsOutcome& res, std::string& err) {
@@ -287,79 +312,21 @@ int emit_tri_bvhs_device_items(const rt_scene_desc& d, uint32_t max_levels, Host
     TriItem* d_items = m.get<TriItem>(n);
     double* d_boxes = m.get<double>((size_t)n * 6);
     uint32_t* d_queue = m.get<uint32_t>(kFixCap);
-    const uint32_t nblk = blocks(n, kScanTile);
-    uint32_t* d_agg = m.get<uint32_t>(nblk);
     Header* d_hdr = m.get<Header>(1);
     TI_SCRATCH_OK();
     for (const Src& a : src)
         if (a.host) TI_TRY(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, st));
     RT_EMIT_MARK("desc upload");
-    const uint32_t* d_mat = (const uint32_t*)src[4].dev;
-    const uint8_t* d_light = (const uint8_t*)src[5].dev;
 
-    ti_init<<<1, 1, 0, st>>>(d_hdr);
+    items_header_clear(d_hdr, st);
     ti_items<<<blocks(n, kTile), kThreads, 0, st>>>((const u64*)src[0].dev, (const u64*)src[1].dev, (const u64*)src[2].dev,
-                                                    (const u64*)src[3].dev, d_mat, n, d.n_shapes, (ulonglong2*)d_items,
-                                                    (ulonglong2*)d_boxes, d_queue, d_hdr);
-    ti_light_reduce<<<nblk, kThreads, 0, st>>>(d_mat, d_light, n, d_agg);
-    ti_light_blocks<<<1, kThreads, 0, st>>>(d_agg, nblk, d_hdr);
+                                                    (const u64*)src[3].dev, (const uint32_t*)src[4].dev, n, d.n_shapes,
+                                                    (ulonglong2*)d_items, (ulonglong2*)d_boxes, d_queue, d_hdr);
     TI_TRY(hipGetLastError());
-    Header h;
-    TI_TRY(hipMemcpyAsync(&h, d_hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-    TI_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < 4; ++k) m.release(src[k].dev);  // vertices, normals, positions, rotations
     RT_EMIT_MARK("items");
-    if (h.n_nan > kFixCap) return kDeviceBuildFallback;  // the host computes every item, as without this path
-    res.n_light = h.n_light;
-
-    // NaN bit patterns are not promised to be the host's: those items come from the host
-    if (h.n_nan) {
-        std::vector<uint32_t> idx(h.n_nan);
-        TI_TRY(hipMemcpy(idx.data(), d_queue, (size_t)h.n_nan * 4, hipMemcpyDeviceToHost));
-        std::vector<TriItem> fix(h.n_nan);
-        for (uint32_t e = 0; e < h.n_nan; ++e) tri_item_of(d, idx[e], fix[e]);
-        TriItem* d_fix = m.get<TriItem>(h.n_nan);
-        TI_SCRATCH_OK();
-        TI_TRY(hipMemcpyAsync(d_fix, fix.data(), (size_t)h.n_nan * sizeof(TriItem), hipMemcpyHostToDevice, st));
-        ti_patch<<<blocks((uint64_t)h.n_nan * kItemParts, kThreads), kThreads, 0, st>>>(
-            (const ulonglong2*)d_fix, d_queue, h.n_nan, (ulonglong2*)d_items, (u64*)d_boxes);
-        TI_TRY(hipGetLastError());
-        TI_TRY(hipStreamSynchronize(st));  // fix is the copy's source until here
-        m.release(d_fix);
-        RT_EMIT_MARK("fix-up");
-    }
-
-    // bvh[5]'s items: the light triangles, in list order
-    TriItem* d_litems = nullptr;
-    double* d_lboxes = nullptr;
-    if (h.n_light) {
-        d_litems = m.get<TriItem>(h.n_light);
-        d_lboxes = m.get<double>((size_t)h.n_light * 6);
-        if (m.oom) {  // bvh[5] alone takes the host path
-            m.oom = false;
-            m.release(d_litems);
-            d_litems = nullptr;
-        } else {
-            TI_SCRATCH_OK();
-            ti_compact<<<nblk, kThreads, 0, st>>>((const ulonglong2*)d_items, (const ulonglong2*)d_boxes, d_mat, d_light, n,
-                                                  d_agg, (ulonglong2*)d_litems, (ulonglong2*)d_lboxes);
-            TI_TRY(hipGetLastError());
-            TI_TRY(hipStreamSynchronize(st));
-        }
-        RT_EMIT_MARK("light compact");
-    }
-    m.release(src[4].dev);
-    m.release(src[5].dev);
-    m.release(d_queue);
-    m.release(d_agg);
-
-    // both BVHs from the one item array; the arena frees the items when this returns
-    res.made[0] = emit_tri_bvh_device_core(m, d_items, d_boxes, n, true, max_levels, tris, err);
-    if (res.made[0] == kDeviceBuildError) { ltris.dev.reset(); return kDeviceBuildError; }
-    m.oom = false;  // an allocation the first BVH missed says nothing about the second
-    if (d_litems) res.made[1] = emit_tri_bvh_device_core(m, d_litems, d_lboxes, h.n_light, false, max_levels, ltris, err);
-    if (res.made[1] == kDeviceBuildError) { tris.dev.reset(); return kDeviceBuildError; }
-    return kDeviceBuildDone;
+    void* const inputs[4] = {src[0].dev, src[1].dev, src[2].dev, src[3].dev};  // vertices, normals, positions, rotations
+    return finish_device_items(m, n, d_items, d_boxes, (uint32_t*)src[4].dev, (uint8_t*)src[5].dev, d_queue, d_hdr, inputs, 4,
+                               desc_item_of, &d, max_levels, tris, ltris, res, err);
 }
 
 }  // namespace rt

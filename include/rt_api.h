@@ -192,6 +192,21 @@ int  rt_scene_create(const rt_scene_desc* desc, rt_scene** out);
 #define RT_BUILD_DEVICE_RECORDS 0x2u
 #define RT_BUILD_DEVICE_ITEMS 0x4u
 int  rt_scene_create_ex(const rt_scene_desc* desc, uint32_t build_flags, rt_scene** out);
+/* Scene creation from a parse result.  Without RT_BUILD_DEVICE_MESHES, or on a parse that
+   is not deferred (rt_load_gltf_ex, RT_GLTF_DEFER), this is rt_parsed_scene_get +
+   rt_scene_create_ex.
+   RT_BUILD_DEVICE_MESHES (valid only with the three flags above, else RT_ERR_INVALID; to
+   rt_scene_create_ex always RT_ERR_INVALID, a description has no meshes): the glTF meshes
+   are flattened on the device.  The referenced buffers are uploaded as they are, with the
+   draw plan and a byte per material, and gltf_items.hip goes from accessor bytes to the
+   items and boxes of RT_BUILD_DEVICE_ITEMS: no description array is made or uploaded.
+   The same bytes again (rt_scene_checksum agrees).  A non-finite POSITION element or an
+   index out of range, anywhere in a drawn accessor, sends the scene to the host flatten,
+   which reports its error as the eager load does; triangles with a NaN are recomputed on
+   the host as above; a BVH the device cannot take gets host items from the description,
+   made then.  build_ms covers the buffers' upload, the flatten, the build and the emission. */
+#define RT_BUILD_DEVICE_MESHES 0x8u
+int  rt_scene_create_parsed(rt_parsed_scene* ps, uint32_t build_flags, rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
 
 typedef struct rt_scene_info {
@@ -203,7 +218,8 @@ typedef struct rt_scene_info {
     uint32_t bvh_depth[6];
     double   build_ms;           /* BVH build (host, or device with RT_BUILD_DEVICE; with
                                     RT_BUILD_DEVICE_RECORDS also the record emission, with
-                                    RT_BUILD_DEVICE_ITEMS the description's upload too) */
+                                    RT_BUILD_DEVICE_ITEMS the description's upload too, with
+                                    RT_BUILD_DEVICE_MESHES the buffers' upload and the flatten) */
     double   upload_ms;          /* H2D copy of what the host made                 */
     uint64_t device_bytes;       /* the scene's arrays; the per-launch workspace (commit
                                     ring, split-tail row buffer <= 256 MB, chunk partials
@@ -238,6 +254,10 @@ typedef struct rt_scene_info {
    computed on the device (RT_BUILD_DEVICE_ITEMS); RT_LAYOUT_DEVICE_RECORDS and
    RT_LAYOUT_DEVICE_BUILT are then set too */
 #define RT_LAYOUT_DEVICE_ITEMS 0x20u
+/* RT_LAYOUT_DEVICE_MESHES: at least one triangle BVH's arrays were written from items
+   flattened on the device from glTF accessor bytes (RT_BUILD_DEVICE_MESHES); the three
+   flags above are then set too */
+#define RT_LAYOUT_DEVICE_MESHES 0x40u
 int rt_scene_get_info(const rt_scene* scene, rt_scene_info* out);
 /* Content hash of the scene's device arrays (BVHs, records, materials; not the
    per-launch workspace), computed on the scene's device.  Two handles built from the
@@ -440,6 +460,22 @@ int rt_parse_custom_scene(const char* text, rt_parsed_scene** out);
    .bin buffers resolved relative to the .gltf path (main.rs:54-59,77-83). */
 int rt_load_gltf(const char* gltf_path, uint32_t width, uint32_t height,
                  uint32_t spp, rt_parsed_scene** out);
+/* rt_load_gltf with flags (0: exactly rt_load_gltf).  RT_GLTF_DEFER: the parse does all
+   that does not depend on the buffers' elements (the JSON and its checks, materials, node
+   transforms, the camera, the buffer files) and, in place of the triangle arrays, records a
+   draw plan: per converted primitive the node matrix and its cofactor matrix, where its
+   POSITION, NORMAL and index elements lie, its material and its triangles' place in the
+   scene.  Where planning meets anything the eager load would report, or an input the
+   device flatten does not take (an accessor without a bufferView, a last element past its
+   buffer's end, a node matrix whose row 3 is not (0, 0, 0, 1), an offset or stride that is
+   no multiple of the component size, more than 2^30 triangles), the call runs the eager
+   load instead and returns what that returns.  rt_parsed_scene_get on a deferred parse
+   makes the description on first use (the host flatten over the plan, cached); the errors
+   that depend on elements (index out of range, non-affine node transform) are reported
+   there, with the eager load's code and message. */
+#define RT_GLTF_DEFER 0x1u
+int rt_load_gltf_ex(const char* gltf_path, uint32_t width, uint32_t height, uint32_t spp,
+                    uint32_t flags, rt_parsed_scene** out);
 /* Views into the parse result (valid until rt_parsed_scene_free). */
 int rt_parsed_scene_get(const rt_parsed_scene* ps, rt_scene_desc* desc,
                         rt_render_params* params);

@@ -80,8 +80,9 @@ def main():
                 left -= k
             views.append({"buffer": 0, "byteOffset": ppos, "byteLength": pnorm - ppos, "target": 34962})
             views.append({"buffer": 0, "byteOffset": pnorm, "byteLength": off - pnorm, "target": 34962})
-            accs.append({"bufferView": len(views) - 2, "componentType": 5126, "count": 3 * cnt, "type": "VEC3",
-                         "min": mn.tolist(), "max": mx.tolist()})
+            # a tone without triangles (--tris < 3) has no bounds: +-inf is no JSON number
+            bounds = {"min": mn.tolist(), "max": mx.tolist()} if cnt else {}
+            accs.append({"bufferView": len(views) - 2, "componentType": 5126, "count": 3 * cnt, "type": "VEC3", **bounds})
             accs.append({"bufferView": len(views) - 1, "componentType": 5126, "count": 3 * cnt, "type": "VEC3"})
             prims.append({"attributes": {"POSITION": len(accs) - 2, "NORMAL": len(accs) - 1}, "material": g,
                           "mode": 4})
