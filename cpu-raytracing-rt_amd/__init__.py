@@ -135,6 +135,12 @@ EXPORTS = {
     "rt_scene_sample_chunks": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32)]),
     "rt_render": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
+    "rt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_void_p, C.c_void_p,
+                                    C.POINTER(rt_stats)]),
+    "rt_render_tiles_moments_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_error_estimate_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "rt_tiles_per_rank": (C.c_int, [C.POINTER(rt_render_params), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rt_sample_chunks": (C.c_int, [C.POINTER(rt_render_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_render_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
@@ -516,6 +522,16 @@ class Scene:
                                None if hits is None else hits.ctypes.data_as(C.c_void_p), C.byref(st)))
         return img, hits, st.as_dict()
 
+    def render_moments(self, params: RenderParams):
+        """(mean, sq), both [H, W, 3] f64 (rt_render_moments): generate_image's mean, bit for
+        bit, and the per-pixel second moment, sum of L * L over the samples / spp."""
+        p = params.to_c()
+        mean = np.zeros((params.height, params.width, 3), np.float64)
+        sq = np.zeros_like(mean)
+        _check(lib().rt_render_moments(self._h, C.byref(p), mean.ctypes.data_as(C.c_void_p),
+                                       sq.ctypes.data_as(C.c_void_p), None))
+        return mean, sq
+
     def intersect(self, rays: np.ndarray) -> np.ndarray:
         """intersect(ray, &scene.primitives, +inf) for rays [n, 6] -> structured hits."""
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
@@ -558,6 +574,12 @@ class Scene:
         p = params.replace(flags=params.flags | (RT_FLAG_STATS if stats else 0)).to_c()
         _check(lib().rt_render_tiles_async(self._h, C.byref(p), rank, world, C.c_void_p(d_out_ptr),
                                            C.c_void_p(stream_ptr)))
+
+    def render_tiles_moments_async(self, params: RenderParams, rank: int, world: int, d_out_ptr: int, d_sq_ptr: int,
+                                   stream_ptr: int = 0):
+        """render_tiles_async with a second packed buffer for the second moment."""
+        _check(lib().rt_render_tiles_moments_async(self._h, C.byref(params.to_c()), rank, world, C.c_void_p(d_out_ptr),
+                                                   C.c_void_p(d_sq_ptr), C.c_void_p(stream_ptr)))
 
     def read_stats(self, reset: bool = True) -> dict:
         st = rt_stats()
@@ -658,6 +680,14 @@ def gather_tiles(tiles, gathered, rank: int, world: int, group=None):
 def unpack_tiles_async(params: RenderParams, world: int, d_gathered_ptr: int, d_image_ptr: int, stream_ptr: int = 0):
     _check(lib().rt_unpack_tiles_async(C.byref(params.to_c()), world, C.c_void_p(d_gathered_ptr),
                                        C.c_void_p(d_image_ptr), C.c_void_p(stream_ptr)))
+
+
+def error_estimate_async(d_mean_ptr: int, d_sq_ptr: int, n_pixels: int, spp: int, d_se_ptr: int, d_summary_ptr: int,
+                         stream_ptr: int = 0):
+    """Device (mean, second moment) [n_pixels][3] f64 -> standard error of the mean (d_se_ptr 0: none)
+    and the 8-double frame summary (rt_error_estimate_async)."""
+    _check(lib().rt_error_estimate_async(C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr), n_pixels, spp,
+                                         C.c_void_p(d_se_ptr), C.c_void_p(d_summary_ptr), C.c_void_p(stream_ptr)))
 
 
 def unpack_tiles_bytes_async(params: RenderParams, world: int, d_gathered_ptr: int, d_bytes_ptr: int,

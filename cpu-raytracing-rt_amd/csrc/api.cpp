@@ -9,7 +9,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -53,6 +55,9 @@ struct rt_scene {
     // chunk partial sums (KParams::chunks > 1), grown on demand
     double* part = nullptr;
     size_t part_entries = 0;
+    // the second partials of a moments frame (rt_render_moments), the same shape, only once one needs them
+    double* part_sq = nullptr;
+    size_t part_sq_entries = 0;
     // persistent path kernel: wave-tile queue and per-wave sample ring
     uint32_t* queue = nullptr;
     double* ring = nullptr;
@@ -146,6 +151,7 @@ void free_scene(rt_scene* s) {
     if (s->spill_n) (void)hipFree(s->spill_n);
     if (s->spill_t) (void)hipFree(s->spill_t);
     if (s->part) (void)hipFree(s->part);
+    if (s->part_sq) (void)hipFree(s->part_sq);
     if (s->queue) (void)hipFree(s->queue);
     if (s->ring) (void)hipFree(s->ring);
     if (s->rows) (void)hipFree(s->rows);
@@ -261,15 +267,16 @@ int ws_idle(rt_scene* s) {
     return RT_OK;
 }
 
-int ensure_part(rt_scene* s, const KParams& k) {
+// part / part_entries: the scene's chunk partials, or its second ones (a moments frame)
+int ensure_part(rt_scene* s, const KParams& k, double*& part, size_t& part_entries) {
     if (k.chunks == 1) return RT_OK;
     const size_t need = (size_t)k.n_slots * k.chunks * 256 * 3;
-    if (need <= s->part_entries) return RT_OK;
+    if (need <= part_entries) return RT_OK;
     if (int rc = ws_idle(s)) return rc;
-    if (s->part) (void)hipFree(s->part);
-    s->part = nullptr; s->part_entries = 0;
-    HIP_TRY(hipMalloc(&s->part, need * sizeof(double)));
-    s->part_entries = need;
+    if (part) (void)hipFree(part);
+    part = nullptr; part_entries = 0;
+    HIP_TRY(hipMalloc(&part, need * sizeof(double)));
+    part_entries = need;
     return RT_OK;
 }
 
@@ -388,7 +395,9 @@ uint32_t path_leaf_batch(const rt_scene* s) {
 
 // Workspace of one path-kernel launch: persistent grid size, then the spill,
 // ring and chunk-partial buffers sized for it (all grow-only, scene-owned).
-int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W) {
+// moments: the frame of rt_render_moments (path_kernel MOM: no stats, no hit ids), whose
+// second partials are sized like the first.
+int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W, bool moments = false) {
     k.suspend = path_suspend(s);
     k.leaf_batch = path_leaf_batch(s);
     const uint64_t n_units = (uint64_t)k.n_slots * k.chunks * 4;
@@ -397,12 +406,13 @@ int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W) {
     W.waves = path_waves(s);
     W.resume = path_resume(s);
     W.kinds = path_pairs(s) ? kKindsPair : (path_compact(s) ? kKindsCompact : path_kinds(s));
-    HIP_TRY(path_grid(stats, hits, W.waves, W.resume, W.kinds, (uint32_t)n_units, &W.grid));
+    HIP_TRY(path_grid(stats, hits, W.waves, W.resume, W.kinds, (uint32_t)n_units, &W.grid, moments));
     const uint64_t lanes = (uint64_t)W.grid * 64u;
     int rc;
     // the 4/5-wave shape-only fused kernel has no LDS stack
     const bool no_lds = W.waves >= 4 && !W.resume && W.kinds == 1;
-    if ((rc = ensure_spill(s, lanes, no_lds)) || (rc = ensure_part(s, k))) return rc;
+    if ((rc = ensure_spill(s, lanes, no_lds)) || (rc = ensure_part(s, k, s->part, s->part_entries))) return rc;
+    if (moments && (rc = ensure_part(s, k, s->part_sq, s->part_sq_entries))) return rc;
     if (!s->queue) HIP_TRY(hipMalloc(&s->queue, kQueueWords * sizeof(uint32_t)));
     const size_t ring_need = (size_t)W.grid * kRingRows * 64 * 3;
     if (ring_need > s->ring_entries) {
@@ -435,9 +445,37 @@ int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W) {
     k.tail_split = tail ? split : 1u;
     s->last_tail_split = k.tail_split;  // rt_scene_get_tuning reports what the frame resolved to
     k.rows = s->rows;
-    W.queue = s->queue; W.ring = s->ring; W.part = s->part;
+    W.queue = s->queue; W.ring = s->ring; W.part = s->part; W.part_sq = s->part_sq;
     W.d_scene = s->d_scene; W.d_params = s->d_params;
     W.spill_n = s->spill_n; W.spill_t = s->spill_t;
+    return RT_OK;
+}
+
+// Scratch of rt_error_estimate_async: se_kernel's per-block partials (render.h kSeMaxBlocks
+// x 8 doubles, 64 KiB).  A fixed pool of kSeSlots per device, handed out round-robin under
+// g_se_mutex; a slot carries the event of its last user, which the next user's stream
+// waits for, so calls on any number of streams never work in one slot at a time.  Made on
+// first use, kept for the life of the process.
+constexpr unsigned kSeSlots = 8;
+struct SeSlot {
+    double* part = nullptr;
+    hipEvent_t done = nullptr;
+};
+struct SePool {
+    SeSlot slots[kSeSlots];
+    unsigned next = 0;
+};
+std::mutex g_se_mutex;
+std::map<int, SePool> g_se_pools;  // by device
+int se_slot_take(hipStream_t st, SeSlot** out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    SePool& pool = g_se_pools[dev];
+    SeSlot& sl = pool.slots[pool.next++ % kSeSlots];
+    if (!sl.part) HIP_TRY(hipMalloc(&sl.part, (size_t)kSeMaxBlocks * 8 * sizeof(double)));
+    if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    else HIP_TRY(hipStreamWaitEvent(st, sl.done, 0));
+    *out = &sl;
     return RT_OK;
 }
 
@@ -840,21 +878,58 @@ int rt_scene_get_tuning(const rt_scene* s, rt_tuning* out) {
     return RT_OK;
 }
 
-int rt_render_tiles_async(rt_scene* s, const rt_render_params* p, uint32_t rank, uint32_t world,
-                          double* d_tile_rgb, void* stream) {
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (!s || !d_tile_rgb) return set_error(RT_ERR_INVALID, "scene/output is NULL");
+// A moments frame has no stats and no hit-id instance (render.hip path_kernel MOM).
+static int check_moments_flags(const rt_render_params* p) {
+    if (p->flags & (RT_FLAG_STATS | RT_FLAG_HIT_IDS))
+        return set_error(RT_ERR_INVALID, "a moments render takes neither RT_FLAG_STATS nor RT_FLAG_HIT_IDS");
+    return RT_OK;
+}
+
+// rt_render_tiles_async (d_tile_sq NULL) and rt_render_tiles_moments_async
+static int render_tiles(rt_scene* s, const rt_render_params* p, uint32_t rank, uint32_t world, double* d_tile_rgb,
+                        double* d_tile_sq, void* stream) {
     if (world == 0 || rank >= world) return set_error(RT_ERR_INVALID, "rank must be < world");
     DEVICE_GUARD(s);
     KParams k = make_kparams(p, rank, world, s->tune.chunk_spp);
     const bool want_stats = (p->flags & RT_FLAG_STATS) != 0;
     PathWork W;
-    if ((rc = prepare_path(s, k, want_stats, false, W))) return rc;
+    if (int rc = prepare_path(s, k, want_stats, false, W, d_tile_sq != nullptr)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     HIP_TRY(ws_begin(s, st));
-    HIP_TRY(launch_path(s->dev, k, W, d_tile_rgb, nullptr, want_stats ? s->d_stats : nullptr, st));
+    HIP_TRY(launch_path(s->dev, k, W, d_tile_rgb, nullptr, want_stats ? s->d_stats : nullptr, st, d_tile_sq));
     HIP_TRY(ws_end(s, st));
+    return RT_OK;
+}
+
+int rt_render_tiles_async(rt_scene* s, const rt_render_params* p, uint32_t rank, uint32_t world,
+                          double* d_tile_rgb, void* stream) {
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!s || !d_tile_rgb) return set_error(RT_ERR_INVALID, "scene/output is NULL");
+    return render_tiles(s, p, rank, world, d_tile_rgb, nullptr, stream);
+}
+
+int rt_render_tiles_moments_async(rt_scene* s, const rt_render_params* p, uint32_t rank, uint32_t world,
+                                  double* d_tile_rgb, double* d_tile_sq, void* stream) {
+    int rc = check_params(p);
+    if (rc || (rc = check_moments_flags(p))) return rc;
+    if (!s || !d_tile_rgb || !d_tile_sq) return set_error(RT_ERR_INVALID, "scene/output is NULL");
+    return render_tiles(s, p, rank, world, d_tile_rgb, d_tile_sq, stream);
+}
+
+int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n_pixels, uint32_t spp, double* d_se,
+                            double* d_summary, void* stream) {
+    if (spp == 0) return set_error(RT_ERR_INVALID, "spp must be > 0");
+    if (!d_summary || ((!d_mean || !d_sq) && n_pixels)) return set_error(RT_ERR_INVALID, "mean/sq/summary is NULL");
+    if (n_pixels > UINT64_MAX / 24) return set_error(RT_ERR_INVALID, "n_pixels too large");
+    if (((uintptr_t)d_mean | (uintptr_t)d_sq | (uintptr_t)d_se) & 15u)
+        return set_error(RT_ERR_INVALID, "mean/sq/se must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g_se_mutex);
+    SeSlot* slot = nullptr;
+    if (int rc = se_slot_take(st, &slot)) return rc;
+    HIP_TRY(launch_error_estimate(d_mean, d_sq, n_pixels, spp, d_se, d_summary, slot->part, st));
+    HIP_TRY(hipEventRecord(slot->done, st));
     return RT_OK;
 }
 
@@ -905,12 +980,11 @@ int rt_tonemap_bytes_async(const double* d_rgb, uint64_t n_pixels, uint8_t* d_by
     return RT_OK;
 }
 
-int rt_render(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, int32_t* opt_hit_ids,
-              rt_stats* opt_stats) {
+// rt_render (out_sq_rgb NULL) and rt_render_moments (no hit ids, no counters)
+static int render_frame(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, double* out_sq_rgb,
+                        int32_t* opt_hit_ids, rt_stats* opt_stats) {
     auto t0 = std::chrono::steady_clock::now();
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (!s || !out_mean_rgb) return set_error(RT_ERR_INVALID, "scene/output is NULL");
+    int rc;
     DEVICE_GUARD(s);
     KParams k = make_kparams(p, 0, 1, s->tune.chunk_spp);
     const uint32_t slots = slots_per_rank(k);
@@ -918,11 +992,15 @@ int rt_render(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, int3
     const bool want_hits = opt_hit_ids && (p->flags & RT_FLAG_HIT_IDS);
     const bool want_stats = opt_stats && (p->flags & RT_FLAG_STATS);
     PathWork W;
-    if ((rc = prepare_path(s, k, want_stats, want_hits, W))) return rc;
-    DevBuf<double> tiles, img;
+    if ((rc = prepare_path(s, k, want_stats, want_hits, W, out_sq_rgb != nullptr))) return rc;
+    DevBuf<double> tiles, img, tiles_sq, img_sq;
     DevBuf<int32_t> hits;
     HIP_TRY(tiles.alloc((size_t)slots * 256 * 3));
     HIP_TRY(img.alloc(npx * 3));
+    if (out_sq_rgb) {
+        HIP_TRY(tiles_sq.alloc((size_t)slots * 256 * 3));
+        HIP_TRY(img_sq.alloc(npx * 3));
+    }
     const uint64_t nhits = npx * p->spp * p->ray_depth;
     if (want_hits) HIP_TRY(hits.alloc(nhits));
     if (want_stats) HIP_TRY(hipMemset(s->d_stats, 0, kStatsWords * sizeof(unsigned long long)));
@@ -932,15 +1010,17 @@ int rt_render(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, int3
     HIP_TRY(ws_begin(s, 0));
     HIP_TRY(hipEventRecord(ev.a, 0));
     hipError_t le = launch_path(s->dev, k, W, tiles.p, want_hits ? hits.p : nullptr,
-                                want_stats ? s->d_stats : nullptr, 0);
+                                want_stats ? s->d_stats : nullptr, 0, tiles_sq.p);
     HIP_TRY(hipEventRecord(ev.b, 0));
     if (le != hipSuccess) return set_error(RT_ERR_DEVICE, std::string("path kernel launch: ") + hipGetErrorString(le));
     HIP_TRY(ws_end(s, 0));
     HIP_TRY(launch_unpack(tiles.p, img.p, p->width, p->height, k.tiles_x, 1, slots, 0));
+    if (out_sq_rgb) HIP_TRY(launch_unpack(tiles_sq.p, img_sq.p, p->width, p->height, k.tiles_x, 1, slots, 0));
     HIP_TRY(hipDeviceSynchronize());
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, ev.a, ev.b);
     HIP_TRY(hipMemcpy(out_mean_rgb, img.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_sq_rgb) HIP_TRY(hipMemcpy(out_sq_rgb, img_sq.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (want_hits) HIP_TRY(hipMemcpy(opt_hit_ids, hits.p, nhits * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (opt_stats) {
         std::memset(opt_stats, 0, sizeof(*opt_stats));
@@ -949,6 +1029,22 @@ int rt_render(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, int3
         opt_stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return RT_OK;
+}
+
+int rt_render(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, int32_t* opt_hit_ids,
+              rt_stats* opt_stats) {
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!s || !out_mean_rgb) return set_error(RT_ERR_INVALID, "scene/output is NULL");
+    return render_frame(s, p, out_mean_rgb, nullptr, opt_hit_ids, opt_stats);
+}
+
+int rt_render_moments(rt_scene* s, const rt_render_params* p, double* out_mean_rgb, double* out_sq_rgb,
+                      rt_stats* opt_stats) {
+    int rc = check_params(p);
+    if (rc || (rc = check_moments_flags(p))) return rc;
+    if (!s || !out_mean_rgb || !out_sq_rgb) return set_error(RT_ERR_INVALID, "scene/output is NULL");
+    return render_frame(s, p, out_mean_rgb, out_sq_rgb, nullptr, opt_stats);
 }
 
 int rt_intersect_rays(rt_scene* s, const double* rays, uint32_t n, rt_hit* out) {

@@ -101,6 +101,7 @@ struct PathWork {
     uint32_t* queue;      // wave-tile counter, zeroed by launch_path
     double* ring;         // [grid][kRing=64][64][3] finished-path radiance
     double* part;         // [n_slots*chunks][256][3] chunk partial sums (chunks > 1)
+    double* part_sq;      // the moments frame's second partials, the same shape (else unused)
     uint32_t* spill_n;    // traversal-stack spill, stride grid*64
     double* spill_t;
 };
@@ -155,9 +156,10 @@ constexpr uint64_t kShapeWavesNodes = 64;  // BVH nodes of a shape-only scene up
 constexpr size_t kQueueWords = 16;  // wave-tile counter (word 0), padded to a 64-B line
 
 hipError_t path_grid(bool stats, bool hits, uint32_t waves, bool resume, int kinds, uint32_t n_units,
-                     uint32_t* grid);
+                     uint32_t* grid, bool moments = false);
+// out_sq: nullptr, or the moments frame's second output in out's layout (then no hit_ids, no stats)
 hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, double* out, int32_t* hit_ids,
-                       unsigned long long* stats, hipStream_t st);
+                       unsigned long long* stats, hipStream_t st, double* out_sq = nullptr);
 hipError_t launch_reduce_chunks(const double* part, double* out, const KParams& P, hipStream_t st);
 // compact: 0 the f64 triangle layout, 1 the compact one, 2 its pair lines (when the scene has them)
 hipError_t launch_trace(const DevScene& S, const double* rays, uint32_t n, rt_hit* out, uint32_t* queue,
@@ -178,6 +180,11 @@ hipError_t launch_unpack_bytes(const double* g, uint8_t* bytes, uint32_t W, uint
                                uint32_t world, uint32_t per_rank, hipStream_t st);
 hipError_t launch_unpack(const double* g, double* img, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t world,
                          uint32_t per_rank, hipStream_t st);
+// moments.hip: (mean, second moment, spp) -> standard error of the mean per value and the
+// frame summary (rt_error_estimate_async); part: kSeMaxBlocks * 8 doubles of scratch
+constexpr uint32_t kSeMaxBlocks = 1024;
+hipError_t launch_error_estimate(const double* mean, const double* sq, uint64_t n_pixels, uint32_t spp, double* se,
+                                 double* summary, double* part, hipStream_t st);
 // ellipsoid records: aux = dev_rcp(radii), the device's own reciprocals (rt_device.h)
 hipError_t launch_ell_rcp(DevShape* shapes, uint32_t n, hipStream_t st);
 // checksum_kernel: order-free content hash of a device array (rt_scene_checksum)

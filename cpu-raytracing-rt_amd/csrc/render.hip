@@ -7,6 +7,8 @@
 //                        quadrant) wave-tiles from a queue; inside one, lanes
 //                        take (sample, pixel) paths dynamically and commit
 //                        radiance per pixel in sample order.
+//                        Its moments instances (MOM) also commit the per-pixel
+//                        sum of squares (rt_render_moments).
 //   reduce_chunks_kernel chunk partial sums -> per-pixel mean
 //   intersect_kernel     batch `intersect` (intersections.rs:42-62), one thread per ray
 //   trace_kernel         the same, persistent: waves refill finished lanes from a queue
@@ -1629,7 +1631,12 @@ RT_D uint32_t unit_of_row(const uint32_t* uq, uint32_t uq_back, uint32_t row) {
 }
 
 
-template <bool ST, bool HIT, int WAVES, bool RES, int KM = 3, bool CMP = false, bool PAIR = false>
+// MOM: the moments instance (rt_render_moments).  The commit carries sq, the sum of
+// v * v over the rows `sum` adds, in the same order, and writes it where `sum` is
+// written into a second output of the same layout.  It exists for ST = HIT = false
+// only, whose hit_ids and stats arguments are unused: they carry the second outputs
+// (out_sq, part_sq), so the plain instances keep their argument list and their code.
+template <bool ST, bool HIT, int WAVES, bool RES, int KM = 3, bool CMP = false, bool PAIR = false, bool MOM = false>
 __global__ __launch_bounds__(kWave, WAVES) void path_kernel(DevScene Sv, KParams Pv,
                                                      const DevScene* __restrict__ Sg,
                                                      const KParams* __restrict__ Pg, double* __restrict__ out,
@@ -1681,6 +1688,8 @@ __global__ __launch_bounds__(kWave, WAVES) void path_kernel(DevScene Sv, KParams
     if (lane < kRing) s_cnt[lane] = 0;
     __syncthreads();
     V3 sum = v3(0.0, 0.0, 0.0);
+    static_assert(!MOM || (!ST && !HIT), "the moments instance has no stats or hit-id form");
+    [[maybe_unused]] V3 sq = v3(0.0, 0.0, 0.0);  // MOM: sum of v * v beside sum
     uint32_t base = 0, next = 0, witers = 0;  // wave-uniform: next row to commit, next path to hand out
     uint32_t open_end = 0;                    // rows of the wave-tiles pulled so far
     uint32_t uq_front = 0, uq_back = 0;       // open wave-tiles: s_uq entries [uq_front, uq_back)
@@ -1884,6 +1893,7 @@ __global__ __launch_bounds__(kWave, WAVES) void path_kernel(DevScene Sv, KParams
                 w[0] = rp[0]; w[1] = rp[1]; w[2] = rp[2];
             } else {
                 sum = sum + v3(rp[0], rp[1], rp[2]);
+                if constexpr (MOM) sq = sq + mul(v3(rp[0], rp[1], rp[2]), v3(rp[0], rp[1], rp[2]));
             }
             __syncthreads();
             if (lane == 0) s_cnt[base % kRing] = 0;
@@ -1899,6 +1909,13 @@ __global__ __launch_bounds__(kWave, WAVES) void path_kernel(DevScene Sv, KParams
                 double* o = (Pt.chunks == 1 ? out : part) + ((uint64_t)e[4] * kBlock + ly * RT_TILE + lx) * 3;
                 o[0] = res.x; o[1] = res.y; o[2] = res.z;
                 sum = v3(0.0, 0.0, 0.0);
+                if constexpr (MOM) {
+                    const V3 rs = own ? (Pt.chunks == 1 ? sq / (double)Pt.spp : sq) : v3(0.0, 0.0, 0.0);
+                    double* o2 = (Pt.chunks == 1 ? (double*)hit_ids : (double*)stats) +
+                                 ((uint64_t)e[4] * kBlock + ly * RT_TILE + lx) * 3;
+                    o2[0] = rs.x; o2[1] = rs.y; o2[2] = rs.z;
+                    sq = v3(0.0, 0.0, 0.0);
+                }
                 ++uq_front;
             }
             ++base;
@@ -2086,50 +2103,53 @@ using PathFn = void (*)(DevScene, KParams, const DevScene*, const KParams*, doub
 // kinds (kShapes | kTris): one-kind instances of the two kernels the host picks
 // by default — the 4-wave resumable kernel for triangle-only scenes (every glTF
 // scene) and the 3-wave fused kernel for shape-only scenes (the Cornell box)
-template <bool ST, bool HIT>
+template <bool ST, bool HIT, bool MOM, int WAVES, bool RES, int KM = 3, bool CMP = false, bool PAIR = false>
+constexpr PathFn path_inst = path_kernel<ST, HIT, WAVES, RES, KM, CMP, PAIR, MOM>;
+template <bool ST, bool HIT, bool MOM = false>
 PathFn path_fn_r(uint32_t waves, bool resume, int kinds) {
 #ifdef RT_ONLY_C2  // experiment builds (tools/variants.py): only the C2 instances, 4x faster to compile
     (void)waves; (void)resume;
 #ifdef RT_C2_W  // experiment: the shape-only fused kernel at RT_C2_W waves/SIMD
-    return kinds == kShapes ? path_kernel<ST, HIT, RT_C2_W, false, kShapes> : path_kernel<ST, HIT, 3, false>;
+    return kinds == kShapes ? path_inst<ST, HIT, MOM, RT_C2_W, false, kShapes> : path_inst<ST, HIT, MOM, 3, false>;
 #else
-    return kinds == kShapes ? path_kernel<ST, HIT, 3, false, kShapes> : path_kernel<ST, HIT, 3, false>;
+    return kinds == kShapes ? path_inst<ST, HIT, MOM, 3, false, kShapes> : path_inst<ST, HIT, MOM, 3, false>;
 #endif
 #elif defined(RT_ONLY_C3)  // ... only the C3 instances
     (void)waves; (void)resume;
 #ifdef RT_C3_W  // experiment: the compact triangle-only kernel at RT_C3_W waves/SIMD
-    if (kinds == kKindsCompact) return path_kernel<ST, HIT, RT_C3_W, true, kTris, true>;
+    if (kinds == kKindsCompact) return path_inst<ST, HIT, MOM, RT_C3_W, true, kTris, true>;
 #else
-    if (kinds == kKindsCompact) return path_kernel<ST, HIT, 4, true, kTris, true>;
+    if (kinds == kKindsCompact) return path_inst<ST, HIT, MOM, 4, true, kTris, true>;
 #endif
-    if (kinds == kKindsPair) return path_kernel<ST, HIT, 4, true, kTris, true, true>;
-    return kinds == kTris ? path_kernel<ST, HIT, 4, true, kTris> : path_kernel<ST, HIT, 4, true>;
+    if (kinds == kKindsPair) return path_inst<ST, HIT, MOM, 4, true, kTris, true, true>;
+    return kinds == kTris ? path_inst<ST, HIT, MOM, 4, true, kTris> : path_inst<ST, HIT, MOM, 4, true>;
 #else
     if (waves == 4 && resume) {
-        if (kinds == kKindsCompact) return path_kernel<ST, HIT, 4, true, kTris, true>;  // compact triangle layout
-        if (kinds == kKindsPair) return path_kernel<ST, HIT, 4, true, kTris, true, true>;  // + pair layout
-        return kinds == kTris ? path_kernel<ST, HIT, 4, true, kTris> : path_kernel<ST, HIT, 4, true>;
+        if (kinds == kKindsCompact) return path_inst<ST, HIT, MOM, 4, true, kTris, true>;  // compact triangle layout
+        if (kinds == kKindsPair) return path_inst<ST, HIT, MOM, 4, true, kTris, true, true>;  // + pair layout
+        return kinds == kTris ? path_inst<ST, HIT, MOM, 4, true, kTris> : path_inst<ST, HIT, MOM, 4, true>;
     }
     kinds &= 3;  // the compact layout has only the triangle-only resumable instance (host: path_kinds)
-    if (waves == 5 && !resume && kinds == kShapes) return path_kernel<ST, HIT, 5, false, kShapes>;  // api.cpp path_waves
-    if (waves == 4) return kinds == kShapes ? path_kernel<ST, HIT, 4, false, kShapes> : path_kernel<ST, HIT, 4, false>;
-    if (resume) return path_kernel<ST, HIT, 3, true>;
-    return kinds == kShapes ? path_kernel<ST, HIT, 3, false, kShapes> : path_kernel<ST, HIT, 3, false>;
+    if (waves == 5 && !resume && kinds == kShapes) return path_inst<ST, HIT, MOM, 5, false, kShapes>;  // api.cpp path_waves
+    if (waves == 4) return kinds == kShapes ? path_inst<ST, HIT, MOM, 4, false, kShapes> : path_inst<ST, HIT, MOM, 4, false>;
+    if (resume) return path_inst<ST, HIT, MOM, 3, true>;
+    return kinds == kShapes ? path_inst<ST, HIT, MOM, 3, false, kShapes> : path_inst<ST, HIT, MOM, 3, false>;
 #endif
 }
-PathFn path_fn(bool stats, bool hits, uint32_t waves, bool resume, int kinds) {
+PathFn path_fn(bool stats, bool hits, uint32_t waves, bool resume, int kinds, bool moments) {
+    if (moments) return path_fn_r<false, false, true>(waves, resume, kinds);  // launch_path: no stats, no hit ids
     if (stats) return hits ? path_fn_r<true, true>(waves, resume, kinds) : path_fn_r<true, false>(waves, resume, kinds);
     return hits ? path_fn_r<false, true>(waves, resume, kinds) : path_fn_r<false, false>(waves, resume, kinds);
 }
 }  // namespace
 
 hipError_t path_grid(bool stats, bool hits, uint32_t waves, bool resume, int kinds, uint32_t n_units,
-                     uint32_t* grid) {
+                     uint32_t* grid, bool moments) {
     int dev = 0, cus = 0, per_cu = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)path_fn(stats, hits, waves, resume, kinds),
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)path_fn(stats, hits, waves, resume, kinds, moments),
                                                      kWave, 0);
     if (e != hipSuccess) return e;
     const uint64_t g = (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(cus, 1);
@@ -2139,10 +2159,14 @@ hipError_t path_grid(bool stats, bool hits, uint32_t waves, bool resume, int kin
 
 __global__ void stage_params_kernel(KParams* dst, KParams P) { *dst = P; }
 __global__ void tail_combine_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part);
+__global__ void tail_combine_sq_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part);
 
+// out_sq != nullptr: the moments frame (path_kernel MOM) — the second moment beside the
+// mean, through the same three steps; no stats, no hit ids.
 hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, double* out, int32_t* hit_ids,
-                       unsigned long long* stats, hipStream_t st) {
+                       unsigned long long* stats, hipStream_t st, double* out_sq) {
     if (P.chunks == 0 || (P.chunks > 1 && !W.part) || !W.queue || !W.ring || W.grid == 0) return hipErrorInvalidValue;
+    if (out_sq && (hit_ids || stats || (P.chunks > 1 && !W.part_sq))) return hipErrorInvalidValue;
     if (W.waves < 3 || W.waves > 5 || (W.waves == 5 && (W.resume || W.kinds != kShapes))) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(W.queue, 0, kQueueWords * sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
@@ -2155,17 +2179,25 @@ hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, d
     hipLaunchKernelGGL(stage_params_kernel, dim3(1), dim3(1), 0, st, W.d_params, P);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(path_fn(stats != nullptr, hit_ids != nullptr, W.waves, W.resume, W.kinds), dim3(W.grid),
-                       dim3(kWave), 0, st,
-                       S, P, W.d_scene, W.d_params, out, W.part, hit_ids, stats, W.spill_n, W.spill_t, W.queue, W.ring);
+    // the moments instance takes its second outputs in the two arguments it does not use
+    hipLaunchKernelGGL(path_fn(stats != nullptr, hit_ids != nullptr, W.waves, W.resume, W.kinds, out_sq != nullptr),
+                       dim3(W.grid), dim3(kWave), 0, st, S, P, W.d_scene, W.d_params, out, W.part,
+                       out_sq ? (int32_t*)out_sq : hit_ids, out_sq ? (unsigned long long*)W.part_sq : stats,
+                       W.spill_n, W.spill_t, W.queue, W.ring);
     e = hipGetLastError();
     if (e == hipSuccess && P.n_tail) {
         hipLaunchKernelGGL(tail_combine_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P,
                            P.n_slots * P.chunks * 4u, out, W.part);
+        if (out_sq)
+            hipLaunchKernelGGL(tail_combine_sq_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P,
+                               P.n_slots * P.chunks * 4u, out_sq, W.part_sq);
         e = hipGetLastError();
     }
     if (e != hipSuccess || P.chunks == 1) return e;
-    return launch_reduce_chunks(W.part, out, P, st);
+    e = launch_reduce_chunks(W.part, out, P, st);
+    // the part_sq runs in run order, divided by spp: the mean's reduction on the second partials
+    if (e == hipSuccess && out_sq) e = launch_reduce_chunks(W.part_sq, out_sq, P, st);
+    return e;
 }
 
 // Content checksum of a device array (rt_scene_checksum; multi.cpp checks every
@@ -2214,6 +2246,25 @@ __global__ void tail_combine_kernel(KParams P, uint32_t n_units, double* __restr
     const uint32_t lx = (g.quad & 1u) * 8u + (lane & 7u), ly = (g.quad >> 1) * 8u + (lane >> 3);
     const bool own = g.tile_ok && g.qx0 + (lane & 7u) < P.width && g.qy0 + (lane >> 3) < P.height;
     const V3 res = own ? (P.chunks == 1 ? sum / (double)P.spp : sum) : v3(0.0, 0.0, 0.0);
+    double* o = (P.chunks == 1 ? out : part) + ((uint64_t)g.oslot * kBlock + ly * RT_TILE + lx) * 3;
+    o[0] = res.x; o[1] = res.y; o[2] = res.z;
+}
+// The moments frame's form (path_kernel MOM): the same rows squared, r * r summed in the same
+// order into the second output — path_kernel's sq, addition for addition.  A kernel of its
+// own, so that tail_combine_kernel stays the code it was.
+__global__ void tail_combine_sq_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part) {
+    const uint32_t lane = threadIdx.x & (kWave - 1), t = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+    if (t >= P.n_tail) return;
+    const UnitGeo g = unit_geo(P, n_units - P.n_tail + t);
+    const double* r = P.rows + ((uint64_t)t * P.chunk_spp * kWave + lane) * 3;
+    V3 sq = v3(0.0, 0.0, 0.0);
+    for (uint32_t k = 0; k < g.nrows; ++k) {
+        const V3 v = v3(r[(uint64_t)k * kWave * 3], r[(uint64_t)k * kWave * 3 + 1], r[(uint64_t)k * kWave * 3 + 2]);
+        sq = sq + mul(v, v);
+    }
+    const uint32_t lx = (g.quad & 1u) * 8u + (lane & 7u), ly = (g.quad >> 1) * 8u + (lane >> 3);
+    const bool own = g.tile_ok && g.qx0 + (lane & 7u) < P.width && g.qy0 + (lane >> 3) < P.height;
+    const V3 res = own ? (P.chunks == 1 ? sq / (double)P.spp : sq) : v3(0.0, 0.0, 0.0);
     double* o = (P.chunks == 1 ? out : part) + ((uint64_t)g.oslot * kBlock + ly * RT_TILE + lx) * 3;
     o[0] = res.x; o[1] = res.y; o[2] = res.z;
 }

@@ -315,6 +315,14 @@ int rt_scene_get_tuning(const rt_scene* scene, rt_tuning* resolved);
    int32 (requires RT_FLAG_HIT_IDS).  opt_stats: NULL or filled. */
 int rt_render(rt_scene* scene, const rt_render_params* params,
               double* out_mean_rgb, int32_t* opt_hit_ids, rt_stats* opt_stats);
+/* rt_render + the per-pixel second moment: out_sq_rgb [H][W][3] f64 = (sum over the
+   pixel's samples, in the order of the mean's sum, of L * L per channel) / spp (chunked frames,
+   rt_scene_sample_chunks: run by run like the mean).  out_mean_rgb is rt_render's, bit
+   for bit, and a pixel with a NaN sample is NaN in both.  Both outputs are required.
+   RT_FLAG_HIT_IDS / RT_FLAG_STATS: RT_ERR_INVALID (the moments kernel has no such
+   form).  opt_stats: NULL, or kernel_ms and total_ms filled, the counters 0. */
+int rt_render_moments(rt_scene* scene, const rt_render_params* params, double* out_mean_rgb,
+                      double* out_sq_rgb, rt_stats* opt_stats);
 
 /* Multi-GPU tile partition: 16x16 tiles, tile t belongs to
    rank t % world.  Each rank renders its tiles into a packed DEVICE buffer
@@ -327,6 +335,25 @@ int rt_tiles_per_rank(const rt_render_params* params, uint32_t world, uint32_t* 
 int rt_render_tiles_async(rt_scene* scene, const rt_render_params* params,
                           uint32_t rank, uint32_t world,
                           double* d_tile_rgb, void* hip_stream);
+/* rt_render_tiles_async with a second packed buffer of the same shape for the second
+   moment (rt_render_moments); both gather and unpack with the existing calls
+   (rt_unpack_tiles_async on each).  Flags as rt_render_moments. */
+int rt_render_tiles_moments_async(rt_scene* scene, const rt_render_params* params,
+                                  uint32_t rank, uint32_t world,
+                                  double* d_tile_rgb, double* d_tile_sq, void* hip_stream);
+/* Standard error of the mean from a frame's mean and second moment, on the current
+   device, stream-ordered.  d_mean, d_sq: [n_pixels][3] f64; d_se: NULL or
+   [n_pixels][3]; all 16-byte aligned.  Per value
+     se = sqrt(max(sq - mean * mean, 0) / (spp - 1)),
+   IEEE sqrt and division, NaN where an input is NaN; spp == 1: +inf (NaN where an
+   input is NaN).  d_summary, 8 doubles, over the frame: [0] the pixels with a
+   non-finite se or mean in any channel; over the other pixels [1..3] the sum of se
+   per channel, [4..6] the sum of the mean per channel, [7] the largest se (0 without
+   such a pixel).  The sums have a fixed order that depends on n_pixels alone: the
+   same bits on every call and stream.  n_pixels == 0: RT_OK, the summary zeroed.
+   Scratch comes from a small per-device pool that orders its users across streams. */
+int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n_pixels, uint32_t spp,
+                            double* d_se, double* d_summary, void* hip_stream);
 
 /* Diagnostics: the scene's raw device counter words (n <= 64), accumulated by
    RT_FLAG_STATS renders: words 0..9 are rt_stats' counters; word 10 counts the
