@@ -42,6 +42,10 @@ RT_TRI_CUSTOM, RT_TRI_GLTF = 0, 1
 RT_FOV_X, RT_FOV_Y = 0, 1
 RT_FLAG_STATS, RT_FLAG_HIT_IDS = 0x1, 0x2
 RT_HIT_MISS, RT_HIT_NONE = -1, -2
+# rt_denoise_params: what a zeroed field means, and the value of normal_squarings for no squaring at all
+RT_DENOISE_ITERATIONS, RT_DENOISE_NORMAL_SQUARINGS = 5, 7
+RT_DENOISE_SIGMA_L, RT_DENOISE_SIGMA_Z, RT_DENOISE_EPS = 4.0, 0.01, 1e-8
+RT_DENOISE_SQUARINGS_NONE = 0xFFFFFFFF
 RT_TILE = 16
 ERRORS = {0: "OK", -1: "INVALID", -2: "DEVICE", -3: "NOMEM", -4: "PARSE", -5: "IO", -6: "UNSUPPORTED"}
 (RT_OK, RT_ERR_INVALID, RT_ERR_DEVICE, RT_ERR_NOMEM, RT_ERR_PARSE, RT_ERR_IO,
@@ -108,6 +112,13 @@ class rt_tuning(C.Structure):
                 ("compact", C.c_int32), ("tail_split", C.c_uint32)]
 
 
+class rt_denoise_params(C.Structure):
+    """Zeroed fields take the header's defaults (RT_DENOISE_*)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32), ("iterations", C.c_uint32),
+                ("normal_squarings", C.c_uint32), ("_pad", C.c_uint32), ("sigma_l", C.c_double),
+                ("sigma_z", C.c_double), ("eps", C.c_double)]
+
+
 TUNING_AUTO = dict(waves=0, resume=-1, kinds=0, suspend_lanes=0, leaf_lanes=0, chunk_spp=0, compact=-1, tail_split=0)
 RT_LAYOUT_COMPACT_TRIS = 0x1
 RT_LAYOUT_PAIR_NODES = 0x4
@@ -141,6 +152,10 @@ EXPORTS = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_error_estimate_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "rt_camera_rays_async": (C.c_int, [C.POINTER(rt_render_params), C.c_void_p, C.c_void_p]),
+    "rt_denoise_workspace_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "rt_denoise_async": (C.c_int, [C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rt_tiles_per_rank": (C.c_int, [C.POINTER(rt_render_params), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rt_sample_chunks": (C.c_int, [C.POINTER(rt_render_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_render_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
@@ -563,6 +578,30 @@ class Scene:
                                               imp.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
         return imp, cnt
 
+    def denoise(self, params: RenderParams, mean: np.ndarray, sq: np.ndarray, **kw):
+        """The à-trous filter (rt_denoise_async) of a frame's (mean, sq) [H, W, 3], as render_moments
+        returns them: pixel-centre rays, their first hits in this scene, the filter; everything
+        between the upload and the download stays on the device.  kw: rt_denoise_params fields
+        (iterations, normal_squarings, sigma_l, sigma_z, eps).  Returns (out [H, W, 3], out_var [H, W]).
+        The buffers are made on torch's current device, where the rays and the filter also run: the
+        scene must live there (it does unless the current device changed since it was created)."""
+        import torch
+        h, w = params.height, params.width
+        dev = dict(dtype=torch.float64, device="cuda")
+        # one allocation each: rt_denoise_async wants every buffer 16-byte aligned, and the second half of a
+        # stacked upload is not when W * H is odd
+        d_mean, d_sq = (torch.from_numpy(np.ascontiguousarray(a, np.float64).reshape(h, w, 3)).cuda() for a in (mean, sq))
+        d_rays, d_hits = torch.empty((h * w, 6), **dev), torch.empty((h * w, 8), **dev)
+        d_out, d_var = torch.empty((h, w, 3), **dev), torch.empty((h, w), **dev)
+        d_ws = torch.empty(denoise_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        camera_rays_async(params, d_rays.data_ptr(), stream)
+        self.intersect_async(d_rays.data_ptr(), h * w, d_hits.data_ptr(), stream_ptr=stream)
+        denoise_async(rt_denoise_params(width=w, height=h, spp=params.spp, **kw), d_mean.data_ptr(),
+                      d_sq.data_ptr(), d_rays.data_ptr(), d_hits.data_ptr(), d_out.data_ptr(), d_var.data_ptr(),
+                      d_ws.data_ptr(), d_ws.numel(), stream)
+        return d_out.cpu().numpy(), d_var.cpu().numpy()
+
     # ---- multi-GPU tile partition (DESIGN.md §5) ----
     def tiles_per_rank(self, params: RenderParams, world: int) -> int:
         n = C.c_uint32()
@@ -688,6 +727,26 @@ def error_estimate_async(d_mean_ptr: int, d_sq_ptr: int, n_pixels: int, spp: int
     and the 8-double frame summary (rt_error_estimate_async)."""
     _check(lib().rt_error_estimate_async(C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr), n_pixels, spp,
                                          C.c_void_p(d_se_ptr), C.c_void_p(d_summary_ptr), C.c_void_p(stream_ptr)))
+
+
+def camera_rays_async(params: RenderParams, d_rays_ptr: int, stream_ptr: int = 0):
+    """Pixel-centre primary rays [H * W][6] f64 of the frame into device memory (rt_camera_rays_async)."""
+    _check(lib().rt_camera_rays_async(C.byref(params.to_c()), C.c_void_p(d_rays_ptr), C.c_void_p(stream_ptr)))
+
+
+def denoise_workspace_bytes(width: int, height: int) -> int:
+    n = C.c_uint64()
+    _check(lib().rt_denoise_workspace_bytes(width, height, C.byref(n)))
+    return n.value
+
+
+def denoise_async(p: rt_denoise_params, d_mean_ptr: int, d_sq_ptr: int, d_rays_ptr: int, d_hits_ptr: int,
+                  d_out_ptr: int, d_out_var_ptr: int, d_workspace_ptr: int, workspace_bytes: int, stream_ptr: int = 0):
+    """Device (mean, second moment, pixel-centre rays, their first hits) -> the filtered frame [H][W][3] f64 and
+    (d_out_var_ptr 0: none) its variance [H][W], in the caller's workspace (rt_denoise_async)."""
+    _check(lib().rt_denoise_async(C.byref(p), C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_rays_ptr),
+                                  C.c_void_p(d_hits_ptr), C.c_void_p(d_out_ptr), C.c_void_p(d_out_var_ptr),
+                                  C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr)))
 
 
 def unpack_tiles_bytes_async(params: RenderParams, world: int, d_gathered_ptr: int, d_bytes_ptr: int,

@@ -933,6 +933,67 @@ int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n
     return RT_OK;
 }
 
+int rt_camera_rays_async(const rt_render_params* p, double* d_rays, void* stream) {
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!d_rays || ((uintptr_t)d_rays & 15u)) return set_error(RT_ERR_INVALID, "rays is NULL or not 16-byte aligned");
+    HIP_TRY(launch_camera_rays(make_kparams(p, 0, 1), d_rays, (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_denoise_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
+    if (!bytes) return set_error(RT_ERR_INVALID, "bytes is NULL");
+    if (width == 0 || height == 0) return set_error(RT_ERR_INVALID, "width/height must be > 0");
+    *bytes = 3 * denoise_buffer_bytes((uint64_t)width * height);
+    return RT_OK;
+}
+
+int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const double* d_sq, const double* d_rays,
+                     const rt_hit* d_hits, double* d_out, double* d_out_var, void* d_workspace,
+                     uint64_t workspace_bytes, void* stream) {
+    if (!p) return set_error(RT_ERR_INVALID, "params is NULL");
+    if (p->width == 0 || p->height == 0) return set_error(RT_ERR_INVALID, "width/height must be > 0");
+    if (p->width > 65535 || p->height > 65535) return set_error(RT_ERR_INVALID, "width/height must be <= 65535");
+    if (p->spp < 2) return set_error(RT_ERR_INVALID, "the variance needs spp >= 2");
+    DenoiseSettings S;
+    S.width = p->width; S.height = p->height; S.spp = p->spp;
+    S.iterations = p->iterations ? p->iterations : RT_DENOISE_ITERATIONS;
+    S.squarings = p->normal_squarings == RT_DENOISE_SQUARINGS_NONE ? 0u
+                  : p->normal_squarings ? p->normal_squarings : RT_DENOISE_NORMAL_SQUARINGS;
+    if (S.iterations > kMaxIterations) return set_error(RT_ERR_INVALID, "iterations must be 1..8 (0: the default)");
+    if (S.squarings > kMaxSquarings)
+        return set_error(RT_ERR_INVALID, "normal_squarings must be 1..10, 0 (default) or RT_DENOISE_SQUARINGS_NONE");
+    const double in[3] = {p->sigma_l, p->sigma_z, p->eps};
+    const double def[3] = {RT_DENOISE_SIGMA_L, RT_DENOISE_SIGMA_Z, RT_DENOISE_EPS};
+    double v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (!(in[i] >= 0.0) || !std::isfinite(in[i]))
+            return set_error(RT_ERR_INVALID, "sigma_l, sigma_z and eps must be finite and > 0 (0: the default)");
+        v[i] = in[i] == 0.0 ? def[i] : in[i];
+    }
+    S.sigma_l = v[0]; S.sigma_z = v[1]; S.eps = v[2];
+    if (!d_mean || !d_sq || !d_rays || !d_hits || !d_out || !d_workspace)
+        return set_error(RT_ERR_INVALID, "mean/sq/rays/hits/out/workspace is NULL");
+    if (((uintptr_t)d_mean | (uintptr_t)d_sq | (uintptr_t)d_rays | (uintptr_t)d_hits | (uintptr_t)d_out |
+         (uintptr_t)d_out_var | (uintptr_t)d_workspace) & 15u)
+        return set_error(RT_ERR_INVALID, "the denoiser's buffers must be 16-byte aligned");
+    const uint64_t n = (uint64_t)p->width * p->height, need = 3 * denoise_buffer_bytes(n);
+    if (workspace_bytes < need)
+        return set_error(RT_ERR_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
+    // an output may overlap neither what the kernels still read nor the other output
+    struct Range { const void* p; uint64_t bytes; };
+    const Range outs[2] = {{d_out, n * 24}, {d_out_var, d_out_var ? n * 8 : 0}};
+    const Range ins[6] = {{d_mean, n * 24}, {d_sq, n * 24}, {d_rays, n * 48}, {d_hits, n * 64}, {d_workspace, need}, outs[1]};
+    for (int o = 0; o < 2; ++o)
+        for (int i = 0; i < 6 - o; ++i) {
+            const uintptr_t a = (uintptr_t)outs[o].p, b = (uintptr_t)ins[i].p;
+            if (outs[o].bytes && ins[i].bytes && a < b + ins[i].bytes && b < a + outs[o].bytes)
+                return set_error(RT_ERR_INVALID, "out/out_var overlaps an input, the workspace or the other output");
+        }
+    HIP_TRY(launch_denoise(S, d_mean, d_sq, d_rays, d_hits, d_out, d_out_var, d_workspace, (hipStream_t)stream));
+    return RT_OK;
+}
+
 int rt_read_stats(rt_scene* s, rt_stats* out, int reset) {
     if (!s || !out) return set_error(RT_ERR_INVALID, "scene/out is NULL");
     DEVICE_GUARD(s);

@@ -185,6 +185,18 @@ hipError_t launch_unpack(const double* g, double* img, uint32_t W, uint32_t H, u
 constexpr uint32_t kSeMaxBlocks = 1024;
 hipError_t launch_error_estimate(const double* mean, const double* sq, uint64_t n_pixels, uint32_t spp, double* se,
                                  double* summary, double* part, hipStream_t st);
+// denoise.hip: pixel-centre camera rays [W*H][6] (rt_camera_rays_async), and the à-trous filter
+// (rt_denoise_async) with rt_denoise_params' defaults resolved (squarings: the count itself).
+// workspace: three buffers of denoise_buffer_bytes(W * H), colour, colour, guide.
+constexpr uint32_t kMaxIterations = 8, kMaxSquarings = 10;
+struct DenoiseSettings {
+    uint32_t width, height, spp, iterations, squarings;
+    double sigma_l, sigma_z, eps;
+};
+hipError_t launch_camera_rays(const KParams& k, double* rays, hipStream_t st);
+uint64_t denoise_buffer_bytes(uint64_t n_pixels);
+hipError_t launch_denoise(const DenoiseSettings& S, const double* mean, const double* sq, const double* rays,
+                          const rt_hit* hits, double* out, double* out_var, void* workspace, hipStream_t st);
 // ellipsoid records: aux = dev_rcp(radii), the device's own reciprocals (rt_device.h)
 hipError_t launch_ell_rcp(DevShape* shapes, uint32_t n, hipStream_t st);
 // checksum_kernel: order-free content hash of a device array (rt_scene_checksum)

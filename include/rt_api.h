@@ -355,6 +355,71 @@ int rt_render_tiles_moments_async(rt_scene* scene, const rt_render_params* param
 int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n_pixels, uint32_t spp,
                             double* d_se, double* d_summary, void* hip_stream);
 
+/* ---- denoiser: a variance-guided a-trous filter (no counterpart in the reference) ----
+   The first consumer of the second moment: it smooths where the estimate is uncertain,
+   stops at geometric edges, and fills non-finite pixels from their valid neighbours.
+   All weights are rational (+ - * / sqrt in a fixed order, IEEE, nothing fused), so the
+   output is a pure function of the inputs and parameters: the same bits on every call,
+   stream and launch geometry, and the bits of a float64 restatement on the host
+   (tests/test_gpu_denoise.py).
+   Preparation, per pixel: per channel v_c = max(sq_c - mean_c * mean_c, 0) / (spp - 1)
+   (max(d, 0) = d < 0 ? 0 : d, a NaN stays); var = (Lr*Lr*v_r + Lg*Lg*v_g) + Lb*Lb*v_b with
+   L = (0.2126, 0.7152, 0.0722); ok = the three mean_c and var all finite.  Guide: hit =
+   (prim != RT_HIT_MISS), n = shading_normal, t, x = origin + t * dir (unfused), each
+   rounded to f32 and widened back to f64 at every use.
+   Iteration i = 0 .. iterations - 1, step s = 2^i: for pixel p the taps q = p + s * (dx, dy),
+   dy = -2..2 outer, dx = -2..2 inner, taps outside the image skipped; h = (1/16, 1/4, 3/8,
+   1/4, 1/16); lum(c) = (Lr*c_r + Lg*c_g) + Lb*c_b.
+     w_g = w_n * w_z when p and q are hits, 1 when both are misses, 0 otherwise;
+       w_n = (d < 0 ? 0 : d), d = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z, squared
+       normal_squarings times; w_z = 1 / (1 + xz*xz), xz = |(n_p.x*e.x + n_p.y*e.y) +
+       n_p.z*e.z| / (sigma_z * t_p), e = x_q - x_p;
+     w_l = 1 / (1 + xl*xl), xl = (lum_q - lum_p) / (sigma_l * sqrt(var_p) + eps), when p is ok,
+       else 1;
+     w = (h[dy] * h[dx]) * (w_g * w_l) when q is ok, else q contributes nothing;
+     in tap order sw = sw + w, sc = sc + w * c_q, sv = sv + (w * w) * var_q.
+   sw > 0: c'_p = sc / sw, var'_p = sv / (sw * sw), p becomes ok (a missing pixel is filled);
+   otherwise c, var and ok of p pass through.  The next iteration reads c', var', ok'. */
+#define RT_DENOISE_ITERATIONS       5u
+#define RT_DENOISE_NORMAL_SQUARINGS 7u    /* w_n = max(0, n_p . n_q)^128 */
+#define RT_DENOISE_SIGMA_L          4.0
+#define RT_DENOISE_SIGMA_Z          0.01
+#define RT_DENOISE_EPS              1e-8
+/* normal_squarings: no squaring at all, w_n = max(0, n_p . n_q) (0 is taken by "default") */
+#define RT_DENOISE_SQUARINGS_NONE   0xffffffffu
+typedef struct rt_denoise_params {
+    uint32_t width, height;
+    uint32_t spp;               /* of the frame that made mean and sq; >= 2                  */
+    uint32_t iterations;        /* 0 = RT_DENOISE_ITERATIONS; 1..8                           */
+    uint32_t normal_squarings;  /* 0 = RT_DENOISE_NORMAL_SQUARINGS; 1..10;
+                                   RT_DENOISE_SQUARINGS_NONE = 0 squarings                   */
+    uint32_t _pad;
+    double sigma_l, sigma_z, eps; /* 0 = RT_DENOISE_SIGMA_L / _SIGMA_Z / _EPS; else finite, > 0 */
+} rt_denoise_params;
+/* Pixel-centre primary rays of the frame, d_rays [H*W][6] f64 = (cam_position, direction),
+   row-major: Camera::fuzzy_ray's arithmetic (camera.rs:48-55) with px + 0.5, py + 0.5 in
+   place of the two random draws, normalised as raytrace does (raytrace.rs:9).  The first
+   hits of these rays (rt_intersect_rays_async) are the denoiser's guide.  Current device,
+   stream-ordered; d_rays 16-byte aligned. */
+int rt_camera_rays_async(const rt_render_params* params, double* d_rays, void* hip_stream);
+/* Bytes of rt_denoise_async's workspace: 96 B per pixel (two colour buffers {r, g, b, var}
+   f64 and the f32 guide), each of the three rounded up to 256 B.  Zero width or height:
+   RT_ERR_INVALID. */
+int rt_denoise_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+/* The filter above on the current device, stream-ordered, in caller-owned memory: no hidden
+   allocation and no scene handle, so calls on different streams share no state.  d_mean,
+   d_sq [H][W][3] f64 (rt_render_moments, or unpacked tiles); d_rays [H*W][6] f64 and d_hits
+   [H*W] the first hit of each (rt_camera_rays_async, rt_intersect_rays_async); d_out
+   [H][W][3] f64, ready for rt_tonemap_bytes_async; d_out_var NULL or [H][W] f64, the
+   filtered var.  All 16-byte aligned.  RT_ERR_INVALID: spp < 2, zero width or height (there
+   is no frame), a parameter out of range, a sigma or eps that is negative or not finite, a
+   NULL required pointer, a workspace too small or misaligned, d_out or d_out_var
+   overlapping an input, the workspace or each other. */
+int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const double* d_sq,
+                     const double* d_rays, const rt_hit* d_hits,
+                     double* d_out, double* d_out_var /* NULL ok */,
+                     void* d_workspace, uint64_t workspace_bytes, void* hip_stream);
+
 /* Diagnostics: the scene's raw device counter words (n <= 64), accumulated by
    RT_FLAG_STATS renders: words 0..9 are rt_stats' counters; word 10 counts the
    last-bounce light queries the timed (no-stats) kernel skips because they cannot
