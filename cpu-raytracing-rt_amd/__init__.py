@@ -119,6 +119,16 @@ class rt_denoise_params(C.Structure):
                 ("sigma_z", C.c_double), ("eps", C.c_double)]
 
 
+class rt_adaptive_layout(C.Structure):
+    """Byte offsets of the adaptive workspace's sub-buffers (rt_adaptive_workspace_bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_tiles", "acc_sum", "acc_sq", "tile_count", "tile_err", "tile_flag",
+                                          "tile_list", "info")]
+
+
+class rt_adaptive_params(C.Structure):
+    _fields_ = [("pass_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_double), ("eps", C.c_double)]
+
+
 TUNING_AUTO = dict(waves=0, resume=-1, kinds=0, suspend_lanes=0, leaf_lanes=0, chunk_spp=0, compact=-1, tail_split=0)
 RT_LAYOUT_COMPACT_TRIS = 0x1
 RT_LAYOUT_PAIR_NODES = 0x4
@@ -156,6 +166,16 @@ EXPORTS = {
     "rt_denoise_workspace_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "rt_denoise_async": (C.c_int, [C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rt_adaptive_workspace_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                                              C.POINTER(rt_adaptive_layout)]),
+    "rt_adaptive_pass_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_void_p, C.c_uint64, C.c_int,
+                                         C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_adaptive_select_async": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_double,
+                                           C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_adaptive_resolve_async": (C.c_int, [C.POINTER(rt_render_params), C.c_void_p, C.c_uint64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(rt_adaptive_params),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
     "rt_tiles_per_rank": (C.c_int, [C.POINTER(rt_render_params), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rt_sample_chunks": (C.c_int, [C.POINTER(rt_render_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_render_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
@@ -547,6 +567,27 @@ class Scene:
                                        sq.ctypes.data_as(C.c_void_p), None))
         return mean, sq
 
+    def render_adaptive(self, params: RenderParams, pass_spp: int, max_spp: int, rel_error: float, eps: float = 0.0):
+        """Adaptive sampling (rt_render_adaptive): passes of pass_spp samples, every tile until its
+        error is <= rel_error or it has max_spp.  Returns (mean, sq [H, W, 3] f64, count [H, W] u32,
+        info: paths = samples spent, kernel_ms, total_ms).  params.spp is ignored."""
+        mean = np.zeros((params.height, params.width, 3), np.float64)
+        sq = np.zeros_like(mean)
+        count = np.zeros((params.height, params.width), np.uint32)
+        a, st = rt_adaptive_params(pass_spp, max_spp, rel_error, eps), rt_stats()
+        _check(lib().rt_render_adaptive(self._h, C.byref(params.to_c()), C.byref(a), mean.ctypes.data_as(C.c_void_p),
+                                        sq.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), C.byref(st)))
+        info = st.as_dict()
+        return mean, sq, count, {k: info[k] for k in ("paths", "kernel_ms", "total_ms")}
+
+    def adaptive_pass_async(self, params: RenderParams, d_workspace_ptr: int, workspace_bytes: int, use_list: bool,
+                            n_list: int, sample_base: int, stream_ptr: int = 0):
+        """One pass of params.spp samples from sample_base onto the workspace's accumulators
+        (rt_adaptive_pass_async): every tile, or the first n_list entries of its tile_list."""
+        _check(lib().rt_adaptive_pass_async(self._h, C.byref(params.to_c()), C.c_void_p(d_workspace_ptr),
+                                            workspace_bytes, 1 if use_list else 0, n_list, sample_base,
+                                            C.c_void_p(stream_ptr)))
+
     def intersect(self, rays: np.ndarray) -> np.ndarray:
         """intersect(ray, &scene.primitives, +inf) for rays [n, 6] -> structured hits."""
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
@@ -747,6 +788,28 @@ def denoise_async(p: rt_denoise_params, d_mean_ptr: int, d_sq_ptr: int, d_rays_p
     _check(lib().rt_denoise_async(C.byref(p), C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_rays_ptr),
                                   C.c_void_p(d_hits_ptr), C.c_void_p(d_out_ptr), C.c_void_p(d_out_var_ptr),
                                   C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr)))
+
+
+def adaptive_workspace(width: int, height: int):
+    """(bytes, layout dict of byte offsets and n_tiles) of the adaptive state (rt_adaptive_workspace_bytes)."""
+    n, lay = C.c_uint64(), rt_adaptive_layout()
+    _check(lib().rt_adaptive_workspace_bytes(width, height, C.byref(n), C.byref(lay)))
+    return n.value, {k: getattr(lay, k) for k, _ in lay._fields_}
+
+
+def adaptive_select_async(width: int, height: int, d_workspace_ptr: int, workspace_bytes: int, threshold: float,
+                          eps: float, pass_spp: int, max_spp: int, stream_ptr: int = 0):
+    """Every tile's error, then the list of the tiles above threshold and info (rt_adaptive_select_async)."""
+    _check(lib().rt_adaptive_select_async(width, height, C.c_void_p(d_workspace_ptr), workspace_bytes, threshold, eps,
+                                          pass_spp, max_spp, C.c_void_p(stream_ptr)))
+
+
+def adaptive_resolve_async(params: RenderParams, d_workspace_ptr: int, workspace_bytes: int, d_mean_ptr: int,
+                           d_sq_ptr: int, d_count_ptr: int = 0, stream_ptr: int = 0):
+    """Accumulators / count -> mean, sq [H][W][3] f64 and (d_count_ptr 0: none) count [H][W] u32."""
+    _check(lib().rt_adaptive_resolve_async(C.byref(params.to_c()), C.c_void_p(d_workspace_ptr), workspace_bytes,
+                                           C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_count_ptr),
+                                           C.c_void_p(stream_ptr)))
 
 
 def unpack_tiles_bytes_async(params: RenderParams, world: int, d_gathered_ptr: int, d_bytes_ptr: int,

@@ -65,6 +65,9 @@ struct rt_scene {
     // rows of the queue's split tail wave-tiles (KParams::rows), grown on demand
     double* rows = nullptr;
     size_t rows_entries = 0;
+    // rt_render_adaptive's state (rt_adaptive_workspace_bytes), grown on demand
+    void* adaptive = nullptr;
+    size_t adaptive_bytes = 0;
     unsigned long long* d_stats = nullptr;
     // the path kernel reads the scene record and the frame constants by pointer
     DevScene* d_scene = nullptr;
@@ -155,6 +158,7 @@ void free_scene(rt_scene* s) {
     if (s->queue) (void)hipFree(s->queue);
     if (s->ring) (void)hipFree(s->ring);
     if (s->rows) (void)hipFree(s->rows);
+    if (s->adaptive) (void)hipFree(s->adaptive);
     if (s->d_stats) (void)hipFree(s->d_stats);
     if (s->d_scene) (void)hipFree(s->d_scene);
     if (s->d_params) (void)hipFree(s->d_params);
@@ -267,9 +271,10 @@ int ws_idle(rt_scene* s) {
     return RT_OK;
 }
 
-// part / part_entries: the scene's chunk partials, or its second ones (a moments frame)
-int ensure_part(rt_scene* s, const KParams& k, double*& part, size_t& part_entries) {
-    if (k.chunks == 1) return RT_OK;
+// part / part_entries: the scene's chunk partials, or its second ones (a moments frame);
+// always: an adaptive pass, whose single run goes to the partials too
+int ensure_part(rt_scene* s, const KParams& k, double*& part, size_t& part_entries, bool always = false) {
+    if (k.chunks == 1 && !always) return RT_OK;
     const size_t need = (size_t)k.n_slots * k.chunks * 256 * 3;
     if (need <= part_entries) return RT_OK;
     if (int rc = ws_idle(s)) return rc;
@@ -396,8 +401,9 @@ uint32_t path_leaf_batch(const rt_scene* s) {
 // Workspace of one path-kernel launch: persistent grid size, then the spill,
 // ring and chunk-partial buffers sized for it (all grow-only, scene-owned).
 // moments: the frame of rt_render_moments (path_kernel MOM: no stats, no hit ids), whose
-// second partials are sized like the first.
-int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W, bool moments = false) {
+// second partials are sized like the first.  An adaptive pass (sums) is sized by its list:
+// k.n_slots is the list's length, and the queue, the grid and the tail split follow from it.
+int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W, bool moments = false, bool sums = false) {
     k.suspend = path_suspend(s);
     k.leaf_batch = path_leaf_batch(s);
     const uint64_t n_units = (uint64_t)k.n_slots * k.chunks * 4;
@@ -411,8 +417,8 @@ int prepare_path(rt_scene* s, KParams& k, bool stats, bool hits, PathWork& W, bo
     int rc;
     // the 4/5-wave shape-only fused kernel has no LDS stack
     const bool no_lds = W.waves >= 4 && !W.resume && W.kinds == 1;
-    if ((rc = ensure_spill(s, lanes, no_lds)) || (rc = ensure_part(s, k, s->part, s->part_entries))) return rc;
-    if (moments && (rc = ensure_part(s, k, s->part_sq, s->part_sq_entries))) return rc;
+    if ((rc = ensure_spill(s, lanes, no_lds)) || (rc = ensure_part(s, k, s->part, s->part_entries, sums))) return rc;
+    if (moments && (rc = ensure_part(s, k, s->part_sq, s->part_sq_entries, sums))) return rc;
     if (!s->queue) HIP_TRY(hipMalloc(&s->queue, kQueueWords * sizeof(uint32_t)));
     const size_t ring_need = (size_t)W.grid * kRingRows * 64 * 3;
     if (ring_need > s->ring_entries) {
@@ -760,7 +766,7 @@ int scene_upload(const HostScene& hs, rt_scene** out, bool replica) {
     }
     HIP_TRY(hipMalloc(&s->d_scene, sizeof(DevScene)));
     HIP_TRY(hipMemcpy(s->d_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&s->d_params, sizeof(KParams)));
+    HIP_TRY(hipMalloc(&s->d_params, sizeof(KParamsSlot)));  // + an adaptive pass's fields
     HIP_TRY(hipMalloc(&s->d_stats, kStatsWords * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(s->d_stats, 0, kStatsWords * sizeof(unsigned long long)));
     s->info.n_planes = d.n_planes;
@@ -1106,6 +1112,147 @@ int rt_render_moments(rt_scene* s, const rt_render_params* p, double* out_mean_r
     if (rc || (rc = check_moments_flags(p))) return rc;
     if (!s || !out_mean_rgb || !out_sq_rgb) return set_error(RT_ERR_INVALID, "scene/output is NULL");
     return render_frame(s, p, out_mean_rgb, out_sq_rgb, nullptr, opt_stats);
+}
+
+/* ---- adaptive sampling (adaptive.hip) ---- */
+static uint64_t frame_tiles(uint32_t width, uint32_t height) {
+    return (uint64_t)((width + RT_TILE - 1) / RT_TILE) * ((height + RT_TILE - 1) / RT_TILE);
+}
+// (no upper limit: only a pass, which check_params guards, packs pixel origins into 16 bits)
+static int check_frame(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0) return set_error(RT_ERR_INVALID, "width/height must be > 0");
+    return RT_OK;
+}
+static int check_adaptive_workspace(uint32_t width, uint32_t height, const void* ws, uint64_t bytes) {
+    if (!ws || ((uintptr_t)ws & 255u)) return set_error(RT_ERR_INVALID, "workspace is NULL or not 256-byte aligned");
+    const uint64_t need = adaptive_layout(frame_tiles(width, height)).bytes;
+    if (bytes < need) return set_error(RT_ERR_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
+    return RT_OK;
+}
+
+int rt_adaptive_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes, rt_adaptive_layout* opt_layout) {
+    if (!bytes) return set_error(RT_ERR_INVALID, "bytes is NULL");
+    if (int rc = check_frame(width, height)) return rc;
+    const AdaptiveLayout L = adaptive_layout(frame_tiles(width, height));
+    *bytes = L.bytes;
+    if (opt_layout) {
+        opt_layout->n_tiles = frame_tiles(width, height);
+        opt_layout->acc_sum = L.acc_sum; opt_layout->acc_sq = L.acc_sq; opt_layout->tile_count = L.tile_count;
+        opt_layout->tile_err = L.tile_err; opt_layout->tile_flag = L.tile_flag; opt_layout->tile_list = L.tile_list;
+        opt_layout->info = L.info;
+    }
+    return RT_OK;
+}
+
+int rt_adaptive_pass_async(rt_scene* s, const rt_render_params* p, void* d_workspace, uint64_t workspace_bytes,
+                           int use_list, uint32_t n_list, uint32_t sample_base, void* stream) {
+    int rc = check_params(p);
+    if (rc || (rc = check_moments_flags(p))) return rc;
+    if (!s) return set_error(RT_ERR_INVALID, "scene is NULL");
+    if (p->spp < 2) return set_error(RT_ERR_INVALID, "a pass needs spp >= 2");
+    if ((uint64_t)sample_base + p->spp > (1ull << 32)) return set_error(RT_ERR_INVALID, "sample_base + spp exceeds 2^32");
+    if ((rc = check_adaptive_workspace(p->width, p->height, d_workspace, workspace_bytes))) return rc;
+    const uint64_t n_tiles = frame_tiles(p->width, p->height);
+    if (use_list && n_list > n_tiles) return set_error(RT_ERR_INVALID, "n_list exceeds the frame's tiles");
+    if (use_list && n_list == 0) return RT_OK;
+    DEVICE_GUARD(s);
+    KParams k = make_kparams(p, 0, 1, s->tune.chunk_spp);
+    const uint32_t* list = nullptr;
+    if (use_list) {
+        list = (const uint32_t*)((char*)d_workspace + adaptive_layout(n_tiles).tile_list);
+        k.n_slots = n_list;
+    }
+    const KList kl{list, k.n_slots, sample_base, 1u, 0u};
+    PathWork W;
+    if ((rc = prepare_path(s, k, false, false, W, true, true))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ws_begin(s, st));
+    // both outputs go to the scene's partials, where a chunked pass's run sums are anyway
+    HIP_TRY(launch_path(s->dev, k, W, W.part, nullptr, nullptr, st, W.part_sq, &kl));
+    HIP_TRY(launch_adaptive_accumulate(d_workspace, n_tiles, W.part, W.part_sq, list, k.n_slots, k.chunks, p->spp,
+                                       sample_base == 0, st));
+    HIP_TRY(ws_end(s, st));
+    return RT_OK;
+}
+
+int rt_adaptive_select_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
+                             double threshold, double eps, uint32_t pass_spp, uint32_t max_spp, void* stream) {
+    int rc = check_frame(width, height);
+    if (rc || (rc = check_adaptive_workspace(width, height, d_workspace, workspace_bytes))) return rc;
+    if (!(threshold >= 0.0)) return set_error(RT_ERR_INVALID, "threshold must be >= 0");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return set_error(RT_ERR_INVALID, "eps must be finite and > 0 (0: the default)");
+    HIP_TRY(launch_adaptive_select(d_workspace, frame_tiles(width, height), threshold, eps == 0.0 ? RT_ADAPTIVE_EPS : eps,
+                                   pass_spp, max_spp, (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_adaptive_resolve_async(const rt_render_params* p, const void* d_workspace, uint64_t workspace_bytes,
+                              double* d_mean, double* d_sq, uint32_t* d_count, void* stream) {
+    int rc = check_params(p);
+    if (rc || (rc = check_adaptive_workspace(p->width, p->height, d_workspace, workspace_bytes))) return rc;
+    if (!d_mean || !d_sq) return set_error(RT_ERR_INVALID, "mean/sq is NULL");
+    HIP_TRY(launch_adaptive_resolve(d_workspace, p->width, p->height, d_mean, d_sq, d_count, (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_render_adaptive(rt_scene* s, const rt_render_params* p, const rt_adaptive_params* a, double* out_mean_rgb,
+                       double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = check_params(p);
+    if (rc || (rc = check_moments_flags(p))) return rc;
+    if (!s || !a || !out_mean_rgb || !out_sq_rgb) return set_error(RT_ERR_INVALID, "scene/adaptive params/output is NULL");
+    if (a->pass_spp < 2 || a->max_spp < a->pass_spp || a->max_spp % a->pass_spp)
+        return set_error(RT_ERR_INVALID, "pass_spp must be >= 2 and max_spp a multiple of it");
+    if (!(a->threshold >= 0.0) || !(a->eps >= 0.0) || !std::isfinite(a->eps))
+        return set_error(RT_ERR_INVALID, "threshold must be >= 0, eps finite and >= 0");
+    DEVICE_GUARD(s);
+    const uint64_t npx = (uint64_t)p->width * p->height;
+    const AdaptiveLayout L = adaptive_layout(frame_tiles(p->width, p->height));
+    if (L.bytes > s->adaptive_bytes) {
+        if ((rc = ws_idle(s))) return rc;
+        if (s->adaptive) (void)hipFree(s->adaptive);
+        s->adaptive = nullptr; s->adaptive_bytes = 0;
+        HIP_TRY(hipMalloc(&s->adaptive, L.bytes));
+        s->adaptive_bytes = L.bytes;
+    }
+    DevBuf<double> mean, sq;
+    DevBuf<uint32_t> count;
+    HIP_TRY(mean.alloc(npx * 3));
+    HIP_TRY(sq.alloc(npx * 3));
+    HIP_TRY(count.alloc(npx));
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventRecord(ev.a, 0));
+    rt_render_params pass = *p;
+    pass.spp = a->pass_spp;
+    uint32_t n_list = 0;
+    for (uint32_t base = 0; base < a->max_spp; base += a->pass_spp) {
+        if ((rc = rt_adaptive_pass_async(s, &pass, s->adaptive, L.bytes, base != 0, n_list, base, nullptr))) return rc;
+        if (base + a->pass_spp >= a->max_spp) break;  // the cap: nothing could be selected
+        if ((rc = rt_adaptive_select_async(p->width, p->height, s->adaptive, L.bytes, a->threshold, a->eps, a->pass_spp,
+                                           a->max_spp, nullptr)))
+            return rc;
+        HIP_TRY(hipMemcpy(&n_list, (char*)s->adaptive + L.info, sizeof(n_list), hipMemcpyDeviceToHost));
+        if (n_list == 0) break;
+    }
+    if ((rc = rt_adaptive_resolve_async(p, s->adaptive, L.bytes, mean.p, sq.p, count.p, nullptr))) return rc;
+    HIP_TRY(hipEventRecord(ev.b, 0));
+    HIP_TRY(hipDeviceSynchronize());
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+    HIP_TRY(hipMemcpy(out_mean_rgb, mean.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_sq_rgb, sq.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> counts;
+    if (!out_count && opt_stats) { counts.resize(npx); out_count = counts.data(); }
+    if (out_count) HIP_TRY(hipMemcpy(out_count, count.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (opt_stats) {
+        std::memset(opt_stats, 0, sizeof(*opt_stats));
+        for (uint64_t i = 0; i < npx; ++i) opt_stats->paths += out_count[i];
+        opt_stats->kernel_ms = ms;
+        opt_stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
 }
 
 int rt_intersect_rays(rt_scene* s, const double* rays, uint32_t n, rt_hit* out) {

@@ -33,6 +33,20 @@ struct KParams {
     uint32_t n_tail, tail_split;
     double* rows;
 };
+// An adaptive pass (adaptive.hip): slot i renders tile tile_list[i], i < n_list (nullptr: the
+// rank's own tiles), the pass's samples are [sample_base, sample_base + spp) of each pixel, and
+// sums != 0 leaves both outputs undivided (sum and sum of squares, not / spp).  Read by the
+// moments instances only, from device memory behind the frame constants (KParamsSlot): as
+// a part of KParams the fields moved the by-value kernel arguments of every instance, and
+// the plain C2 frame ran 0.4% slower (profiles/r13/bench_c2_pair_byvalue.log).
+struct KList {
+    const uint32_t* tile_list;
+    uint32_t n_list, sample_base, sums, pad_;
+};
+struct KParamsSlot {  // the scene's device slot (PathWork::d_params points at k)
+    KParams k;
+    KList l;
+};
 
 // device work counters: paths, segments, aabb, tri, shape, shaded, light queries,
 // light hits, lane steps, wave steps (64 x longest lane) — rt_stats order
@@ -158,9 +172,25 @@ constexpr size_t kQueueWords = 16;  // wave-tile counter (word 0), padded to a 6
 hipError_t path_grid(bool stats, bool hits, uint32_t waves, bool resume, int kinds, uint32_t n_units,
                      uint32_t* grid, bool moments = false);
 // out_sq: nullptr, or the moments frame's second output in out's layout (then no hit_ids, no stats)
+// list: nullptr, or a moments frame's adaptive-pass fields
 hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, double* out, int32_t* hit_ids,
-                       unsigned long long* stats, hipStream_t st, double* out_sq = nullptr);
+                       unsigned long long* stats, hipStream_t st, double* out_sq = nullptr, const KList* list = nullptr);
 hipError_t launch_reduce_chunks(const double* part, double* out, const KParams& P, hipStream_t st);
+// adaptive.hip: the device side of rt_adaptive_*_async.  The workspace is one caller-owned
+// block; adaptive_layout gives its sub-buffers' byte offsets (each a multiple of 256).
+struct AdaptiveLayout {
+    uint64_t acc_sum, acc_sq, tile_count, tile_err, tile_flag, tile_list, info, bytes;
+};
+AdaptiveLayout adaptive_layout(uint64_t n_tiles);
+constexpr uint32_t kCompactThreads = 1024;  // as_compact's block: tiles per trip
+// part / part_sq: the pass's run sums [n_list][chunks][256][3]; list: nullptr for slot == tile
+hipError_t launch_adaptive_accumulate(void* ws, uint64_t n_tiles, const double* part, const double* part_sq,
+                                      const uint32_t* list, uint32_t n_list, uint32_t chunks, uint32_t pass_spp,
+                                      bool first, hipStream_t st);
+hipError_t launch_adaptive_select(void* ws, uint64_t n_tiles, double threshold, double eps, uint32_t pass_spp,
+                                  uint32_t max_spp, hipStream_t st);
+hipError_t launch_adaptive_resolve(const void* ws, uint32_t W, uint32_t H, double* mean, double* sq, uint32_t* count,
+                                   hipStream_t st);
 // compact: 0 the f64 triangle layout, 1 the compact one, 2 its pair lines (when the scene has them)
 hipError_t launch_trace(const DevScene& S, const double* rays, uint32_t n, rt_hit* out, uint32_t* queue,
                         uint32_t* spill_n, double* spill_t, uint32_t grid, int compact, hipStream_t st);

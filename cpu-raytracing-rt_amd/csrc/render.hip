@@ -1568,19 +1568,35 @@ struct UnitGeo {
     uint32_t quad;
     bool tile_ok;
 };
-RT_D UnitGeo unit_geo(const KParams& P, uint32_t unit) {
+// LIST (the moments instances): the adaptive-pass fields *L apply.  The tile of a slot then
+// comes from L->tile_list, one wave-uniform read through the scalar cache (the list is
+// written by an earlier launch, as_compact or the caller, never by this one), and the
+// wave-tile's first sample starts at L->sample_base; nrows, and so a split tail's row
+// offsets, stay those of the pass's own spp.
+template <bool LIST = false>
+RT_D UnitGeo unit_geo(const KParams& P, uint32_t unit, [[maybe_unused]] const KList* L = nullptr) {
     UnitGeo g;
     g.quad = unit & 3u;
     const uint32_t sci = unit >> 2;  // slot * chunks + chunk
     const uint32_t slot = sci / P.chunks, chunk = sci % P.chunks;
-    const uint64_t tile = (uint64_t)P.rank + (uint64_t)slot * P.world;
+    uint64_t tile = (uint64_t)P.rank + (uint64_t)slot * P.world;
+    if constexpr (LIST) {
+        if (L->tile_list) tile = slot < L->n_list ? uni(L->tile_list)[slot] : P.n_tiles;
+    }
     g.tile_ok = tile < P.n_tiles;
     g.qx0 = (uint32_t)(tile % P.tiles_x) * RT_TILE + (g.quad & 1u) * 8u;
     g.qy0 = (uint32_t)(tile / P.tiles_x) * RT_TILE + (g.quad >> 1) * 8u;
     g.s0 = chunk * P.chunk_spp;
     g.nrows = min(P.spp, g.s0 + P.chunk_spp) - g.s0;
+    if constexpr (LIST) g.s0 += L->sample_base;
     g.oslot = P.chunks == 1 ? slot : sci;  // out[slot] (means) or part[sci] (chunk sums)
     return g;
+}
+// the one output of a single-run frame is the mean, sum / spp — or, in an adaptive pass, the sum
+template <bool LIST>
+RT_D bool divides(const KParams& P, [[maybe_unused]] const KList* L) {
+    if constexpr (LIST) return P.chunks == 1 && !L->sums;
+    return P.chunks == 1;
 }
 // The queue's tail (round 5, DESIGN.md §5 "per-launch tail"): the last P.n_tail
 // wave-tiles are handed out as P.tail_split parts of consecutive rows each, so the
@@ -1591,11 +1607,13 @@ RT_D UnitGeo unit_geo(const KParams& P, uint32_t unit) {
 // is bit-identical whatever the split (and for any rank count).  Queue entry q:
 // q < n_units - n_tail a whole wave-tile, else part (q - first) % split of tail
 // wave-tile (q - first) / split.  Returns false for an empty part.
-RT_D bool queue_entry(const KParams& P, uint32_t n_units, uint32_t q, UnitGeo& g, uint32_t& tail, uint32_t& roff) {
+template <bool LIST = false>
+RT_D bool queue_entry(const KParams& P, uint32_t n_units, uint32_t q, UnitGeo& g, uint32_t& tail, uint32_t& roff,
+                      const KList* L = nullptr) {
     const uint32_t first = n_units - P.n_tail;
-    if (q < first) { g = unit_geo(P, q); tail = ~0u; roff = 0; return true; }
+    if (q < first) { g = unit_geo<LIST>(P, q, L); tail = ~0u; roff = 0; return true; }
     const uint32_t j = q - first, t = j / P.tail_split, part = j % P.tail_split;
-    g = unit_geo(P, first + t);
+    g = unit_geo<LIST>(P, first + t, L);
     const uint32_t r0 = g.nrows * part / P.tail_split, r1 = g.nrows * (part + 1) / P.tail_split;
     g.s0 += r0;
     g.nrows = r1 - r0;
@@ -1731,7 +1749,9 @@ __global__ __launch_bounds__(kWave, WAVES) void path_kernel(DevScene Sv, KParams
             }
             UnitGeo g;
             uint32_t tail, roff;
-            if (!queue_entry(Pt, n_units, unit, g, tail, roff)) continue;  // an empty tail part
+            if constexpr (MOM) {  // the adaptive-pass fields lie behind the frame constants (render.h KParamsSlot)
+                if (!queue_entry<true>(Pt, n_units, unit, g, tail, roff, opaque((const KList*)(Pg + 1)))) continue;
+            } else if (!queue_entry(Pt, n_units, unit, g, tail, roff)) continue;  // an empty tail part
             if (lane == 0) store_unit(s_uq + (uq_back % kUQ) * kUW, open_end, g, tail, roff);
             open_end += g.nrows;
             ++uq_back;
@@ -1905,12 +1925,14 @@ __global__ __launch_bounds__(kWave, WAVES) void path_kernel(DevScene Sv, KParams
                 const uint32_t lx = (quad & 1u) * 8u + (lane & 7u), ly = (quad >> 1) * 8u + (lane >> 3);
                 const bool own = (e[5] & 1u) && (qxy & 0xFFFFu) + (lane & 7u) < Pt.width &&
                                  (qxy >> 16) + (lane >> 3) < Pt.height;
-                const V3 res = own ? (Pt.chunks == 1 ? sum / (double)Pt.spp : sum) : v3(0.0, 0.0, 0.0);
+                [[maybe_unused]] const KList* Lp = nullptr;
+                if constexpr (MOM) Lp = opaque((const KList*)(Pg + 1));
+                const V3 res = own ? (divides<MOM>(Pt, Lp) ? sum / (double)Pt.spp : sum) : v3(0.0, 0.0, 0.0);
                 double* o = (Pt.chunks == 1 ? out : part) + ((uint64_t)e[4] * kBlock + ly * RT_TILE + lx) * 3;
                 o[0] = res.x; o[1] = res.y; o[2] = res.z;
                 sum = v3(0.0, 0.0, 0.0);
                 if constexpr (MOM) {
-                    const V3 rs = own ? (Pt.chunks == 1 ? sq / (double)Pt.spp : sq) : v3(0.0, 0.0, 0.0);
+                    const V3 rs = own ? (divides<true>(Pt, Lp) ? sq / (double)Pt.spp : sq) : v3(0.0, 0.0, 0.0);
                     double* o2 = (Pt.chunks == 1 ? (double*)hit_ids : (double*)stats) +
                                  ((uint64_t)e[4] * kBlock + ly * RT_TILE + lx) * 3;
                     o2[0] = rs.x; o2[1] = rs.y; o2[2] = rs.z;
@@ -2158,13 +2180,19 @@ hipError_t path_grid(bool stats, bool hits, uint32_t waves, bool resume, int kin
 }
 
 __global__ void stage_params_kernel(KParams* dst, KParams P) { *dst = P; }
+__global__ void stage_list_kernel(KParamsSlot* dst, KList L) { dst->l = L; }
 __global__ void tail_combine_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part);
-__global__ void tail_combine_sq_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part);
+__global__ void tail_combine_list_kernel(KParams P, KList L, uint32_t n_units, double* __restrict__ out,
+                                         double* __restrict__ part);
+__global__ void tail_combine_sq_kernel(KParams P, KList L, uint32_t n_units, double* __restrict__ out,
+                                       double* __restrict__ part);
 
 // out_sq != nullptr: the moments frame (path_kernel MOM) — the second moment beside the
 // mean, through the same three steps; no stats, no hit ids.
 hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, double* out, int32_t* hit_ids,
-                       unsigned long long* stats, hipStream_t st, double* out_sq) {
+                       unsigned long long* stats, hipStream_t st, double* out_sq, const KList* list) {
+    if (list && !out_sq) return hipErrorInvalidValue;  // only the moments instances read it
+    const KList L = list ? *list : KList{nullptr, 0u, 0u, 0u, 0u};
     if (P.chunks == 0 || (P.chunks > 1 && !W.part) || !W.queue || !W.ring || W.grid == 0) return hipErrorInvalidValue;
     if (out_sq && (hit_ids || stats || (P.chunks > 1 && !W.part_sq))) return hipErrorInvalidValue;
     if (W.waves < 3 || W.waves > 5 || (W.waves == 5 && (W.resume || W.kinds != kShapes))) return hipErrorInvalidValue;
@@ -2177,6 +2205,7 @@ hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, d
     // the frame constants travel by pointer (see opaque): stage them in the scene's
     // slot, stream-ordered (the by-value argument is captured at launch)
     hipLaunchKernelGGL(stage_params_kernel, dim3(1), dim3(1), 0, st, W.d_params, P);
+    if (out_sq) hipLaunchKernelGGL(stage_list_kernel, dim3(1), dim3(1), 0, st, (KParamsSlot*)W.d_params, L);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // the moments instance takes its second outputs in the two arguments it does not use
@@ -2186,14 +2215,19 @@ hipError_t launch_path(const DevScene& S, const KParams& P, const PathWork& W, d
                        W.spill_n, W.spill_t, W.queue, W.ring);
     e = hipGetLastError();
     if (e == hipSuccess && P.n_tail) {
-        hipLaunchKernelGGL(tail_combine_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P,
-                           P.n_slots * P.chunks * 4u, out, W.part);
-        if (out_sq)
-            hipLaunchKernelGGL(tail_combine_sq_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P,
+        if (!out_sq) {
+            hipLaunchKernelGGL(tail_combine_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P,
+                               P.n_slots * P.chunks * 4u, out, W.part);
+        } else {
+            hipLaunchKernelGGL(tail_combine_list_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P, L,
+                               P.n_slots * P.chunks * 4u, out, W.part);
+            hipLaunchKernelGGL(tail_combine_sq_kernel, dim3((P.n_tail + 3) / 4), dim3(4 * kWave), 0, st, P, L,
                                P.n_slots * P.chunks * 4u, out_sq, W.part_sq);
+        }
         e = hipGetLastError();
     }
-    if (e != hipSuccess || P.chunks == 1) return e;
+    // an adaptive pass takes the run sums as they are (adaptive.hip as_accumulate)
+    if (e != hipSuccess || P.chunks == 1 || L.sums) return e;
     e = launch_reduce_chunks(W.part, out, P, st);
     // the part_sq runs in run order, divided by spp: the mean's reduction on the second partials
     if (e == hipSuccess && out_sq) e = launch_reduce_chunks(W.part_sq, out_sq, P, st);
@@ -2235,27 +2269,38 @@ hipError_t launch_checksum(const void* p, uint64_t bytes, unsigned long long* d_
 // The queue's tail wave-tiles (queue_entry): each pixel's rows summed in sample order
 // from v3(0) — path_kernel's commit, addition for addition — and written where that
 // commit writes (means when chunks == 1, else the chunk partial).
-__global__ void tail_combine_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part) {
+template <bool LIST>
+RT_D void tail_combine(const KParams& P, const KList* L, uint32_t n_units, double* __restrict__ out,
+                       double* __restrict__ part) {
     const uint32_t lane = threadIdx.x & (kWave - 1), t = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
     if (t >= P.n_tail) return;
-    const UnitGeo g = unit_geo(P, n_units - P.n_tail + t);
+    const UnitGeo g = unit_geo<LIST>(P, n_units - P.n_tail + t, L);
     const double* r = P.rows + ((uint64_t)t * P.chunk_spp * kWave + lane) * 3;
     V3 sum = v3(0.0, 0.0, 0.0);
     for (uint32_t k = 0; k < g.nrows; ++k) sum = sum + v3(r[(uint64_t)k * kWave * 3], r[(uint64_t)k * kWave * 3 + 1],
                                                           r[(uint64_t)k * kWave * 3 + 2]);
     const uint32_t lx = (g.quad & 1u) * 8u + (lane & 7u), ly = (g.quad >> 1) * 8u + (lane >> 3);
     const bool own = g.tile_ok && g.qx0 + (lane & 7u) < P.width && g.qy0 + (lane >> 3) < P.height;
-    const V3 res = own ? (P.chunks == 1 ? sum / (double)P.spp : sum) : v3(0.0, 0.0, 0.0);
+    const V3 res = own ? (divides<LIST>(P, L) ? sum / (double)P.spp : sum) : v3(0.0, 0.0, 0.0);
     double* o = (P.chunks == 1 ? out : part) + ((uint64_t)g.oslot * kBlock + ly * RT_TILE + lx) * 3;
     o[0] = res.x; o[1] = res.y; o[2] = res.z;
+}
+__global__ void tail_combine_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part) {
+    tail_combine<false>(P, nullptr, n_units, out, part);
+}
+// the moments frame's, with the adaptive-pass fields (unit_geo LIST)
+__global__ void tail_combine_list_kernel(KParams P, KList L, uint32_t n_units, double* __restrict__ out,
+                                         double* __restrict__ part) {
+    tail_combine<true>(P, &L, n_units, out, part);
 }
 // The moments frame's form (path_kernel MOM): the same rows squared, r * r summed in the same
 // order into the second output — path_kernel's sq, addition for addition.  A kernel of its
 // own, so that tail_combine_kernel stays the code it was.
-__global__ void tail_combine_sq_kernel(KParams P, uint32_t n_units, double* __restrict__ out, double* __restrict__ part) {
+__global__ void tail_combine_sq_kernel(KParams P, KList L, uint32_t n_units, double* __restrict__ out,
+                                       double* __restrict__ part) {
     const uint32_t lane = threadIdx.x & (kWave - 1), t = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
     if (t >= P.n_tail) return;
-    const UnitGeo g = unit_geo(P, n_units - P.n_tail + t);
+    const UnitGeo g = unit_geo<true>(P, n_units - P.n_tail + t, &L);
     const double* r = P.rows + ((uint64_t)t * P.chunk_spp * kWave + lane) * 3;
     V3 sq = v3(0.0, 0.0, 0.0);
     for (uint32_t k = 0; k < g.nrows; ++k) {
@@ -2264,7 +2309,7 @@ __global__ void tail_combine_sq_kernel(KParams P, uint32_t n_units, double* __re
     }
     const uint32_t lx = (g.quad & 1u) * 8u + (lane & 7u), ly = (g.quad >> 1) * 8u + (lane >> 3);
     const bool own = g.tile_ok && g.qx0 + (lane & 7u) < P.width && g.qy0 + (lane >> 3) < P.height;
-    const V3 res = own ? (P.chunks == 1 ? sq / (double)P.spp : sq) : v3(0.0, 0.0, 0.0);
+    const V3 res = own ? (divides<true>(P, &L) ? sq / (double)P.spp : sq) : v3(0.0, 0.0, 0.0);
     double* o = (P.chunks == 1 ? out : part) + ((uint64_t)g.oslot * kBlock + ly * RT_TILE + lx) * 3;
     o[0] = res.x; o[1] = res.y; o[2] = res.z;
 }

@@ -420,6 +420,80 @@ int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const dou
                      double* d_out, double* d_out_var /* NULL ok */,
                      void* d_workspace, uint64_t workspace_bytes, void* hip_stream);
 
+/* ---- adaptive sampling: error-driven passes over a device-built tile list ----
+   A frame is rendered in passes of pass_spp samples.  The first pass covers every 16x16 tile;
+   after each pass the device measures every tile's error and lists the tiles still above a
+   threshold, and the next pass renders only those, continuing each pixel's sample sequence
+   where it stopped: a pass at sample base b draws samples [b, b + spp) of its pixels, the
+   samples a plain frame of more spp draws (the RNG is keyed by seed, pixel and sample index).
+   A tile that received j passes of a samples, each cut into runs of c (rt_scene_sample_chunks
+   of a frame of `a` spp; c divides a), holds the sums of a plain frame of j * a spp with runs
+   of c, bit for bit: a pass's run sums are added onto the accumulators one by one, in order.
+   State, in one caller-owned block (rt_adaptive_workspace_bytes; offsets in rt_adaptive_layout,
+   each a multiple of 256), n = tiles_x * tiles_y tiles, tile t = ty * tiles_x + tx:
+     acc_sum, acc_sq  [n][256][3] f64  per-pixel sum of L and of L * L, the packed tile layout of
+                                       rt_render_tiles_async (pixels outside the image: zeros)
+     tile_count       [n] u32          samples every pixel of the tile has received
+     tile_err         [n] f64          the tile's error (below); +inf: not measured (count < 2)
+     tile_flag        [n] u32          1: the tile has a pixel whose error is not finite
+     tile_list        [n] u32          the tiles selected for the next pass, ascending
+     info             16 B             {u32 n_list, u32 n_flagged, f64 max_err}
+   The error of a pixel with n = tile_count samples, per channel c, IEEE and nothing fused:
+     mean_c = sum_c / n, m2_c = sq_c / n, v_c = max(m2_c - mean_c * mean_c, 0) / (n - 1)
+     (max(d, 0) = d < 0 ? 0 : d, the denoiser's), var = (Lr*Lr*v_r + Lg*Lg*v_g) + Lb*Lb*v_b,
+     lum = (Lr*mean_r + Lg*mean_g) + Lb*mean_b, L the denoiser's, e = sqrt(var) / (lum + eps):
+   the standard error of the pixel's luminance relative to the luminance.  A tile's error is
+   the largest finite e of its pixels (0 without one).  A pixel whose e is NaN or infinite
+   (a NaN sample: more samples cannot repair it) sets tile_flag and holds no tile open.
+   eps keeps black pixels finite: with the default a pixel below 1e-3 of display white is
+   measured against 1e-3, an absolute floor (a definition, not a tuned number). */
+#define RT_ADAPTIVE_EPS 1e-3
+typedef struct rt_adaptive_layout {
+    uint64_t n_tiles;
+    uint64_t acc_sum, acc_sq, tile_count, tile_err, tile_flag, tile_list, info; /* byte offsets */
+} rt_adaptive_layout;
+typedef struct rt_adaptive_params {
+    uint32_t pass_spp;  /* samples a pass adds; >= 2                                   */
+    uint32_t max_spp;   /* cap per pixel; a multiple of pass_spp                       */
+    double threshold;   /* a tile whose error is <= threshold is done; >= 0, +inf ok   */
+    double eps;         /* 0 = RT_ADAPTIVE_EPS; else finite, > 0                       */
+} rt_adaptive_params;
+/* Bytes of the state above; opt_layout NULL or filled.  Zero width or height: RT_ERR_INVALID. */
+int rt_adaptive_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes, rt_adaptive_layout* opt_layout);
+/* One pass: params->spp (>= 2) samples from sample_base for every tile (use_list == 0) or
+   for the first n_list entries of the workspace's tile_list, rendered by the moments kernel
+   and added onto the accumulators; tile_count += spp.  A pass at sample_base 0 starts its
+   tiles: their accumulators are set, not added to, their count becomes spp and their error
+   "not measured", so an all-tiles pass at base 0 initialises a fresh workspace.  A list
+   entry >= n_tiles is skipped; an entry that occurs twice is undefined.  Ordered on the
+   scene's workspace like every render (Conventions: Streams).  RT_ERR_INVALID: hit-id or
+   stats flags, spp < 2, n_list > n_tiles, sample_base + spp > 2^32, a workspace that is NULL,
+   too small or not 256-byte aligned.  use_list with n_list == 0: RT_OK, nothing launched. */
+int rt_adaptive_pass_async(rt_scene* scene, const rt_render_params* params, void* d_workspace,
+                           uint64_t workspace_bytes, int use_list, uint32_t n_list, uint32_t sample_base,
+                           void* hip_stream);
+/* Measure and select, on the current device, stream-ordered, no scene: tile_err and
+   tile_flag of every tile whose count is below max_spp (a tile at the cap keeps what it
+   had), then tile_list = the tiles with err > threshold && count + pass_spp <= max_spp in
+   ascending order, and info = {their number, the flagged tiles, the largest finite
+   tile_err}.  The same bytes on every call and stream.  RT_ERR_INVALID: threshold negative
+   or NaN, eps negative or not finite, the workspace as above. */
+int rt_adaptive_select_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
+                             double threshold, double eps, uint32_t pass_spp, uint32_t max_spp, void* hip_stream);
+/* The frame from the state: d_mean, d_sq [H][W][3] f64 = acc / tile_count, d_count NULL or
+   [H][W] u32.  d_mean is ready for rt_tonemap_bytes_async; (d_mean, d_sq) are what
+   rt_error_estimate_async and rt_denoise_async take only when the count is uniform. */
+int rt_adaptive_resolve_async(const rt_render_params* params, const void* d_workspace, uint64_t workspace_bytes,
+                              double* d_mean, double* d_sq, uint32_t* d_count /* NULL ok */, void* hip_stream);
+/* The loop on the host: a pass over all tiles at base 0; select; read info (16 bytes); a pass
+   over the list at base k * pass_spp; ... until the list is empty or max_spp is reached; resolve.
+   params->spp is ignored.  out_mean_rgb, out_sq_rgb [H][W][3] f64 required, out_count NULL or
+   [H][W] u32.  The state lives in the scene's grow-only workspace.  opt_stats: paths = the
+   samples spent, kernel_ms = device time from the first pass to the resolve (the info
+   read-backs included), total_ms; the other counters 0. */
+int rt_render_adaptive(rt_scene* scene, const rt_render_params* params, const rt_adaptive_params* adaptive,
+                       double* out_mean_rgb, double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats);
+
 /* Diagnostics: the scene's raw device counter words (n <= 64), accumulated by
    RT_FLAG_STATS renders: words 0..9 are rt_stats' counters; word 10 counts the
    last-bounce light queries the timed (no-stats) kernel skips because they cannot
