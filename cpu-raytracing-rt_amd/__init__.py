@@ -176,6 +176,14 @@ EXPORTS = {
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(rt_adaptive_params),
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
+    "rt_adaptive_select_rank_async": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_double,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_render_adaptive_rank": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.POINTER(rt_adaptive_params),
+                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
+    "rt_error_estimate_counts_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "rt_denoise_counts_async": (C.c_int, [C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rt_tiles_per_rank": (C.c_int, [C.POINTER(rt_render_params), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rt_sample_chunks": (C.c_int, [C.POINTER(rt_render_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_render_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
@@ -567,16 +575,21 @@ class Scene:
                                        sq.ctypes.data_as(C.c_void_p), None))
         return mean, sq
 
-    def render_adaptive(self, params: RenderParams, pass_spp: int, max_spp: int, rel_error: float, eps: float = 0.0):
+    def render_adaptive(self, params: RenderParams, pass_spp: int, max_spp: int, rel_error: float, eps: float = 0.0,
+                        rank: int = 0):
         """Adaptive sampling (rt_render_adaptive): passes of pass_spp samples, every tile until its
-        error is <= rel_error or it has max_spp.  Returns (mean, sq [H, W, 3] f64, count [H, W] u32,
-        info: paths = samples spent, kernel_ms, total_ms).  params.spp is ignored."""
+        error is <= rel_error or it has max_spp.  rank != 0: the tile's error is its (rank + 1)-th largest
+        pixel error, not the largest (rt_render_adaptive_rank).  Returns (mean, sq [H, W, 3] f64, count
+        [H, W] u32, info: paths = samples spent, kernel_ms, total_ms).  params.spp is ignored."""
         mean = np.zeros((params.height, params.width, 3), np.float64)
         sq = np.zeros_like(mean)
         count = np.zeros((params.height, params.width), np.uint32)
         a, st = rt_adaptive_params(pass_spp, max_spp, rel_error, eps), rt_stats()
-        _check(lib().rt_render_adaptive(self._h, C.byref(params.to_c()), C.byref(a), mean.ctypes.data_as(C.c_void_p),
-                                        sq.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), C.byref(st)))
+        out = (mean.ctypes.data_as(C.c_void_p), sq.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), C.byref(st))
+        if rank:
+            _check(lib().rt_render_adaptive_rank(self._h, C.byref(params.to_c()), C.byref(a), rank, *out))
+        else:
+            _check(lib().rt_render_adaptive(self._h, C.byref(params.to_c()), C.byref(a), *out))
         info = st.as_dict()
         return mean, sq, count, {k: info[k] for k in ("paths", "kernel_ms", "total_ms")}
 
@@ -619,10 +632,12 @@ class Scene:
                                               imp.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
         return imp, cnt
 
-    def denoise(self, params: RenderParams, mean: np.ndarray, sq: np.ndarray, **kw):
+    def denoise(self, params: RenderParams, mean: np.ndarray, sq: np.ndarray, count: Optional[np.ndarray] = None, **kw):
         """The à-trous filter (rt_denoise_async) of a frame's (mean, sq) [H, W, 3], as render_moments
         returns them: pixel-centre rays, their first hits in this scene, the filter; everything
-        between the upload and the download stays on the device.  kw: rt_denoise_params fields
+        between the upload and the download stays on the device.  count: None, or [H, W] u32 as
+        render_adaptive returns it, every pixel's own sample count in place of params.spp
+        (rt_denoise_counts_async).  kw: rt_denoise_params fields
         (iterations, normal_squarings, sigma_l, sigma_z, eps).  Returns (out [H, W, 3], out_var [H, W]).
         The buffers are made on torch's current device, where the rays and the filter also run: the
         scene must live there (it does unless the current device changed since it was created)."""
@@ -638,9 +653,13 @@ class Scene:
         stream = torch.cuda.current_stream().cuda_stream
         camera_rays_async(params, d_rays.data_ptr(), stream)
         self.intersect_async(d_rays.data_ptr(), h * w, d_hits.data_ptr(), stream_ptr=stream)
-        denoise_async(rt_denoise_params(width=w, height=h, spp=params.spp, **kw), d_mean.data_ptr(),
-                      d_sq.data_ptr(), d_rays.data_ptr(), d_hits.data_ptr(), d_out.data_ptr(), d_var.data_ptr(),
-                      d_ws.data_ptr(), d_ws.numel(), stream)
+        tail = (d_rays.data_ptr(), d_hits.data_ptr(), d_out.data_ptr(), d_var.data_ptr(), d_ws.data_ptr(), d_ws.numel(), stream)
+        p = rt_denoise_params(width=w, height=h, spp=params.spp, **kw)
+        if count is None:
+            denoise_async(p, d_mean.data_ptr(), d_sq.data_ptr(), *tail)
+        else:
+            d_count = torch.from_numpy(np.ascontiguousarray(count, np.uint32).reshape(h, w).view(np.int32)).cuda()
+            denoise_counts_async(p, d_mean.data_ptr(), d_sq.data_ptr(), d_count.data_ptr(), *tail)
         return d_out.cpu().numpy(), d_var.cpu().numpy()
 
     # ---- multi-GPU tile partition ----
@@ -770,6 +789,14 @@ def error_estimate_async(d_mean_ptr: int, d_sq_ptr: int, n_pixels: int, spp: int
                                          C.c_void_p(d_se_ptr), C.c_void_p(d_summary_ptr), C.c_void_p(stream_ptr)))
 
 
+def error_estimate_counts_async(d_mean_ptr: int, d_sq_ptr: int, d_count_ptr: int, n_pixels: int, d_se_ptr: int,
+                                d_summary_ptr: int, stream_ptr: int = 0):
+    """error_estimate_async with every pixel's own count, [n_pixels] u32 (rt_error_estimate_counts_async)."""
+    _check(lib().rt_error_estimate_counts_async(C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_count_ptr),
+                                                n_pixels, C.c_void_p(d_se_ptr), C.c_void_p(d_summary_ptr),
+                                                C.c_void_p(stream_ptr)))
+
+
 def camera_rays_async(params: RenderParams, d_rays_ptr: int, stream_ptr: int = 0):
     """Pixel-centre primary rays [H * W][6] f64 of the frame into device memory (rt_camera_rays_async)."""
     _check(lib().rt_camera_rays_async(C.byref(params.to_c()), C.c_void_p(d_rays_ptr), C.c_void_p(stream_ptr)))
@@ -790,6 +817,16 @@ def denoise_async(p: rt_denoise_params, d_mean_ptr: int, d_sq_ptr: int, d_rays_p
                                   C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr)))
 
 
+def denoise_counts_async(p: rt_denoise_params, d_mean_ptr: int, d_sq_ptr: int, d_count_ptr: int, d_rays_ptr: int,
+                         d_hits_ptr: int, d_out_ptr: int, d_out_var_ptr: int, d_workspace_ptr: int, workspace_bytes: int,
+                         stream_ptr: int = 0):
+    """denoise_async with every pixel's own count, [H][W] u32, in place of p.spp (rt_denoise_counts_async)."""
+    _check(lib().rt_denoise_counts_async(C.byref(p), C.c_void_p(d_mean_ptr), C.c_void_p(d_sq_ptr),
+                                         C.c_void_p(d_count_ptr), C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
+                                         C.c_void_p(d_out_ptr), C.c_void_p(d_out_var_ptr), C.c_void_p(d_workspace_ptr),
+                                         workspace_bytes, C.c_void_p(stream_ptr)))
+
+
 def adaptive_workspace(width: int, height: int):
     """(bytes, layout dict of byte offsets and n_tiles) of the adaptive state (rt_adaptive_workspace_bytes)."""
     n, lay = C.c_uint64(), rt_adaptive_layout()
@@ -802,6 +839,13 @@ def adaptive_select_async(width: int, height: int, d_workspace_ptr: int, workspa
     """Every tile's error, then the list of the tiles above threshold and info (rt_adaptive_select_async)."""
     _check(lib().rt_adaptive_select_async(width, height, C.c_void_p(d_workspace_ptr), workspace_bytes, threshold, eps,
                                           pass_spp, max_spp, C.c_void_p(stream_ptr)))
+
+
+def adaptive_select_rank_async(width: int, height: int, d_workspace_ptr: int, workspace_bytes: int, threshold: float,
+                               eps: float, pass_spp: int, max_spp: int, rank: int, stream_ptr: int = 0):
+    """adaptive_select_async with a tile's (rank + 1)-th largest pixel error as its error (rt_adaptive_select_rank_async)."""
+    _check(lib().rt_adaptive_select_rank_async(width, height, C.c_void_p(d_workspace_ptr), workspace_bytes, threshold,
+                                               eps, pass_spp, max_spp, rank, C.c_void_p(stream_ptr)))
 
 
 def adaptive_resolve_async(params: RenderParams, d_workspace_ptr: int, workspace_bytes: int, d_mean_ptr: int,

@@ -3,6 +3,7 @@
 //
 //   as_accumulate  a pass's run sums onto the accumulators of the tiles it rendered
 //   as_metric      every tile's error from its accumulators
+//   as_metric_rank the same with a ranked pixel error in place of the largest (by counting in LDS)
 //   as_compact     the tiles still above the threshold, as a list in tile order, and `info`
 //   as_resolve     accumulators / count -> the frame, row-major
 //
@@ -154,6 +155,72 @@ __global__ __launch_bounds__(kThreads) void as_metric(const double2* __restrict_
     }
 }
 
+// as_metric with the (r + 1)-th largest of the tile's 256 values g in place of the largest,
+// r = rank * m / 256 for a tile with m pixels inside the image (rt_adaptive_select_rank_async).
+// g is finite and >= +0, so doubles order as their bit patterns and the keys are the u64s.
+// Selection by counting, no sort: every lane puts its key into LDS, and after the one barrier
+// (which the flags share) counts the keys that come before its own in the order "larger key
+// first, equal keys by pixel index".  That order is total, so the 256 counts are a
+// permutation of 0..255 and exactly one lane finds r: it writes its key, one of the inputs,
+// unchanged.  The keys are read as 128 sixteen-byte words at addresses every lane shares:
+// broadcasts, no bank conflicts, and no traffic beyond the 2 KiB of keys.
+__global__ __launch_bounds__(kThreads) void as_metric_rank(const double2* __restrict__ acc_sum,
+                                                           const double2* __restrict__ acc_sq,
+                                                           const uint32_t* __restrict__ tile_count, uint32_t max_spp,
+                                                           double eps, uint32_t W, uint32_t H, uint32_t tiles_x,
+                                                           uint32_t rank, double* __restrict__ tile_err,
+                                                           uint32_t* __restrict__ tile_flag) {
+    __shared__ double2 s_sum[kTileWords], s_sq[kTileWords];
+    __shared__ ulonglong2 s_key[kThreads / 2];
+    __shared__ uint32_t s_bad[kWaves];
+    const uint64_t tile = blockIdx.x;
+    const uint32_t count = tile_count[tile];
+    if (count >= max_spp) return;  // as as_metric: block-uniform exits
+    if (count < 2) {
+        if (threadIdx.x == 0) { tile_err[tile] = INFINITY; tile_flag[tile] = 0u; }
+        return;
+    }
+    stage_tile(s_sum, s_sq, acc_sum, acc_sq, tile);
+    // e as as_metric computes it, restated: sharing the lines through a function reorders
+    // as_metric's own instructions, and that kernel stays as it was compiled
+    const double* ps = (const double*)s_sum + kPixelDoubles * threadIdx.x;
+    const double* pq = (const double*)s_sq + kPixelDoubles * threadIdx.x;
+    const double n = (double)count, n1 = n - 1.0;
+    double mean[3], v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mean[c] = ps[c] / n;
+        const double m2 = pq[c] / n;
+        const double d = m2 - mean[c] * mean[c];
+        v[c] = (d < 0.0 ? 0.0 : d) / n1;
+    }
+    const double var = ((kLr * kLr) * v[0] + (kLg * kLg) * v[1]) + (kLb * kLb) * v[2];
+    const double lum = (kLr * mean[0] + kLg * mean[1]) + kLb * mean[2];
+    const double e = sqrt(var) / (lum + eps);
+    const bool bad = !finite(e);
+    const unsigned long long key = (unsigned long long)__double_as_longlong(!bad && e > 0.0 ? e : 0.0);
+    ((unsigned long long*)s_key)[threadIdx.x] = key;
+    const bool any_bad = __ballot(bad) != 0;
+    if ((threadIdx.x & 63u) == 0) s_bad[threadIdx.x >> 6] = any_bad ? 1u : 0u;
+    __syncthreads();
+    uint32_t before = 0;  // keys ahead of this lane's
+#pragma unroll 8
+    for (uint32_t j = 0; j < kThreads; j += 2) {
+        const ulonglong2 k = s_key[j / 2];
+        before += (k.x > key || (k.x == key && j < threadIdx.x)) ? 1u : 0u;
+        before += (k.y > key || (k.y == key && j + 1 < threadIdx.x)) ? 1u : 0u;
+    }
+    // the tile's pixels inside the image scale the rank: a full tile uses rank itself
+    const uint32_t x0 = (uint32_t)(tile % tiles_x) * RT_TILE, y0 = (uint32_t)(tile / tiles_x) * RT_TILE;
+    const uint32_t m = min((uint32_t)RT_TILE, W - x0) * min((uint32_t)RT_TILE, H - y0);
+    if (before == rank * m / 256u) {
+        uint32_t f = s_bad[0];
+        for (uint32_t k = 1; k < kWaves; ++k) f |= s_bad[k];
+        tile_err[tile] = __longlong_as_double((long long)key);
+        tile_flag[tile] = f;
+    }
+}
+
 // -------------------------------------------------------------------- compact ----
 struct AsInfo {
     uint32_t n_list, n_flagged;
@@ -266,6 +333,14 @@ hipError_t launch_adaptive_accumulate(void* ws, uint64_t n_tiles, const double* 
     return hipGetLastError();
 }
 
+static hipError_t launch_compact(char* b, const AdaptiveLayout& L, uint64_t n_tiles, double threshold,
+                                 uint32_t pass_spp, uint32_t max_spp, hipStream_t st) {
+    hipLaunchKernelGGL(as_compact, dim3(1), dim3(kCompactThreads), 0, st, (const double*)(b + L.tile_err),
+                       (const uint32_t*)(b + L.tile_count), (const uint32_t*)(b + L.tile_flag), n_tiles, threshold,
+                       pass_spp, max_spp, (uint32_t*)(b + L.tile_list), (AsInfo*)(b + L.info));
+    return hipGetLastError();
+}
+
 hipError_t launch_adaptive_select(void* ws, uint64_t n_tiles, double threshold, double eps, uint32_t pass_spp,
                                   uint32_t max_spp, hipStream_t st) {
     const AdaptiveLayout L = adaptive_layout(n_tiles);
@@ -273,12 +348,21 @@ hipError_t launch_adaptive_select(void* ws, uint64_t n_tiles, double threshold, 
     hipLaunchKernelGGL(as_metric, dim3((unsigned)n_tiles), dim3(kThreads), 0, st, (const double2*)(b + L.acc_sum),
                        (const double2*)(b + L.acc_sq), (const uint32_t*)(b + L.tile_count), max_spp, eps,
                        (double*)(b + L.tile_err), (uint32_t*)(b + L.tile_flag));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(as_compact, dim3(1), dim3(kCompactThreads), 0, st, (const double*)(b + L.tile_err),
-                       (const uint32_t*)(b + L.tile_count), (const uint32_t*)(b + L.tile_flag), n_tiles, threshold,
-                       pass_spp, max_spp, (uint32_t*)(b + L.tile_list), (AsInfo*)(b + L.info));
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_compact(b, L, n_tiles, threshold, pass_spp, max_spp, st);
+}
+
+hipError_t launch_adaptive_select_rank(void* ws, uint32_t W, uint32_t H, double threshold, double eps,
+                                       uint32_t pass_spp, uint32_t max_spp, uint32_t rank, hipStream_t st) {
+    const uint32_t tiles_x = (W + RT_TILE - 1) / RT_TILE, tiles_y = (H + RT_TILE - 1) / RT_TILE;
+    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
+    const AdaptiveLayout L = adaptive_layout(n_tiles);
+    char* b = (char*)ws;
+    hipLaunchKernelGGL(as_metric_rank, dim3((unsigned)n_tiles), dim3(kThreads), 0, st, (const double2*)(b + L.acc_sum),
+                       (const double2*)(b + L.acc_sq), (const uint32_t*)(b + L.tile_count), max_spp, eps, W, H, tiles_x,
+                       rank, (double*)(b + L.tile_err), (uint32_t*)(b + L.tile_flag));
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_compact(b, L, n_tiles, threshold, pass_spp, max_spp, st);
 }
 
 hipError_t launch_adaptive_resolve(const void* ws, uint32_t W, uint32_t H, double* mean, double* sq, uint32_t* count,

@@ -923,9 +923,9 @@ int rt_render_tiles_moments_async(rt_scene* s, const rt_render_params* p, uint32
     return render_tiles(s, p, rank, world, d_tile_rgb, d_tile_sq, stream);
 }
 
-int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n_pixels, uint32_t spp, double* d_se,
-                            double* d_summary, void* stream) {
-    if (spp == 0) return set_error(RT_ERR_INVALID, "spp must be > 0");
+// d_count: nullptr (spp holds), or every pixel's own count (spp unused)
+static int error_estimate(const double* d_mean, const double* d_sq, const uint32_t* d_count, uint64_t n_pixels,
+                          uint32_t spp, double* d_se, double* d_summary, void* stream) {
     if (!d_summary || ((!d_mean || !d_sq) && n_pixels)) return set_error(RT_ERR_INVALID, "mean/sq/summary is NULL");
     if (n_pixels > UINT64_MAX / 24) return set_error(RT_ERR_INVALID, "n_pixels too large");
     if (((uintptr_t)d_mean | (uintptr_t)d_sq | (uintptr_t)d_se) & 15u)
@@ -934,9 +934,21 @@ int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n
     std::lock_guard<std::mutex> lock(g_se_mutex);
     SeSlot* slot = nullptr;
     if (int rc = se_slot_take(st, &slot)) return rc;
-    HIP_TRY(launch_error_estimate(d_mean, d_sq, n_pixels, spp, d_se, d_summary, slot->part, st));
+    HIP_TRY(launch_error_estimate(d_mean, d_sq, n_pixels, spp, d_se, d_summary, slot->part, st, d_count));
     HIP_TRY(hipEventRecord(slot->done, st));
     return RT_OK;
+}
+
+int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n_pixels, uint32_t spp, double* d_se,
+                            double* d_summary, void* stream) {
+    if (spp == 0) return set_error(RT_ERR_INVALID, "spp must be > 0");
+    return error_estimate(d_mean, d_sq, nullptr, n_pixels, spp, d_se, d_summary, stream);
+}
+
+int rt_error_estimate_counts_async(const double* d_mean, const double* d_sq, const uint32_t* d_count, uint64_t n_pixels,
+                                   double* d_se, double* d_summary, void* stream) {
+    if (!d_count || ((uintptr_t)d_count & 3u)) return set_error(RT_ERR_INVALID, "count is NULL or not 4-byte aligned");
+    return error_estimate(d_mean, d_sq, d_count, n_pixels, 0, d_se, d_summary, stream);
 }
 
 int rt_camera_rays_async(const rt_render_params* p, double* d_rays, void* stream) {
@@ -954,13 +966,16 @@ int rt_denoise_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes)
     return RT_OK;
 }
 
-int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const double* d_sq, const double* d_rays,
-                     const rt_hit* d_hits, double* d_out, double* d_out_var, void* d_workspace,
-                     uint64_t workspace_bytes, void* stream) {
+// counts: d_count [H][W] u32 is required and p->spp is not looked at; else d_count is nullptr
+static int denoise(const rt_denoise_params* p, const double* d_mean, const double* d_sq, const uint32_t* d_count,
+                   bool counts, const double* d_rays, const rt_hit* d_hits, double* d_out, double* d_out_var,
+                   void* d_workspace, uint64_t workspace_bytes, void* stream) {
     if (!p) return set_error(RT_ERR_INVALID, "params is NULL");
     if (p->width == 0 || p->height == 0) return set_error(RT_ERR_INVALID, "width/height must be > 0");
     if (p->width > 65535 || p->height > 65535) return set_error(RT_ERR_INVALID, "width/height must be <= 65535");
-    if (p->spp < 2) return set_error(RT_ERR_INVALID, "the variance needs spp >= 2");
+    if (!counts && p->spp < 2) return set_error(RT_ERR_INVALID, "the variance needs spp >= 2");
+    if (counts && (!d_count || ((uintptr_t)d_count & 3u)))
+        return set_error(RT_ERR_INVALID, "count is NULL or not 4-byte aligned");
     DenoiseSettings S;
     S.width = p->width; S.height = p->height; S.spp = p->spp;
     S.iterations = p->iterations ? p->iterations : RT_DENOISE_ITERATIONS;
@@ -989,15 +1004,30 @@ int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const dou
     // an output may overlap neither what the kernels still read nor the other output
     struct Range { const void* p; uint64_t bytes; };
     const Range outs[2] = {{d_out, n * 24}, {d_out_var, d_out_var ? n * 8 : 0}};
-    const Range ins[6] = {{d_mean, n * 24}, {d_sq, n * 24}, {d_rays, n * 48}, {d_hits, n * 64}, {d_workspace, need}, outs[1]};
+    const Range ins[7] = {{d_count, counts ? n * 4 : 0}, {d_mean, n * 24}, {d_sq, n * 24}, {d_rays, n * 48},
+                          {d_hits, n * 64}, {d_workspace, need}, outs[1]};
     for (int o = 0; o < 2; ++o)
-        for (int i = 0; i < 6 - o; ++i) {
+        for (int i = 0; i < 7 - o; ++i) {
             const uintptr_t a = (uintptr_t)outs[o].p, b = (uintptr_t)ins[i].p;
             if (outs[o].bytes && ins[i].bytes && a < b + ins[i].bytes && b < a + outs[o].bytes)
                 return set_error(RT_ERR_INVALID, "out/out_var overlaps an input, the workspace or the other output");
         }
-    HIP_TRY(launch_denoise(S, d_mean, d_sq, d_rays, d_hits, d_out, d_out_var, d_workspace, (hipStream_t)stream));
+    if (counts && (uintptr_t)d_count < (uintptr_t)d_workspace + need && (uintptr_t)d_workspace < (uintptr_t)d_count + n * 4)
+        return set_error(RT_ERR_INVALID, "count overlaps the workspace");
+    HIP_TRY(launch_denoise(S, d_mean, d_sq, d_rays, d_hits, d_out, d_out_var, d_workspace, (hipStream_t)stream, d_count));
     return RT_OK;
+}
+
+int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const double* d_sq, const double* d_rays,
+                     const rt_hit* d_hits, double* d_out, double* d_out_var, void* d_workspace,
+                     uint64_t workspace_bytes, void* stream) {
+    return denoise(p, d_mean, d_sq, nullptr, false, d_rays, d_hits, d_out, d_out_var, d_workspace, workspace_bytes, stream);
+}
+
+int rt_denoise_counts_async(const rt_denoise_params* p, const double* d_mean, const double* d_sq,
+                            const uint32_t* d_count, const double* d_rays, const rt_hit* d_hits, double* d_out,
+                            double* d_out_var, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    return denoise(p, d_mean, d_sq, d_count, true, d_rays, d_hits, d_out, d_out_var, d_workspace, workspace_bytes, stream);
 }
 
 int rt_read_stats(rt_scene* s, rt_stats* out, int reset) {
@@ -1175,15 +1205,34 @@ int rt_adaptive_pass_async(rt_scene* s, const rt_render_params* p, void* d_works
     return RT_OK;
 }
 
-int rt_adaptive_select_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
-                             double threshold, double eps, uint32_t pass_spp, uint32_t max_spp, void* stream) {
+// rank < 0: the largest pixel error (as_metric); else the ranked one (as_metric_rank)
+static int adaptive_select(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes, double threshold,
+                           double eps, uint32_t pass_spp, uint32_t max_spp, int rank, void* stream) {
     int rc = check_frame(width, height);
     if (rc || (rc = check_adaptive_workspace(width, height, d_workspace, workspace_bytes))) return rc;
     if (!(threshold >= 0.0)) return set_error(RT_ERR_INVALID, "threshold must be >= 0");
     if (!(eps >= 0.0) || !std::isfinite(eps)) return set_error(RT_ERR_INVALID, "eps must be finite and > 0 (0: the default)");
-    HIP_TRY(launch_adaptive_select(d_workspace, frame_tiles(width, height), threshold, eps == 0.0 ? RT_ADAPTIVE_EPS : eps,
-                                   pass_spp, max_spp, (hipStream_t)stream));
+    if (rank > 255) return set_error(RT_ERR_INVALID, "rank must be 0..255");
+    eps = eps == 0.0 ? RT_ADAPTIVE_EPS : eps;
+    if (rank < 0)
+        HIP_TRY(launch_adaptive_select(d_workspace, frame_tiles(width, height), threshold, eps, pass_spp, max_spp,
+                                       (hipStream_t)stream));
+    else
+        HIP_TRY(launch_adaptive_select_rank(d_workspace, width, height, threshold, eps, pass_spp, max_spp, (uint32_t)rank,
+                                            (hipStream_t)stream));
     return RT_OK;
+}
+
+int rt_adaptive_select_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
+                             double threshold, double eps, uint32_t pass_spp, uint32_t max_spp, void* stream) {
+    return adaptive_select(width, height, d_workspace, workspace_bytes, threshold, eps, pass_spp, max_spp, -1, stream);
+}
+
+int rt_adaptive_select_rank_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
+                                  double threshold, double eps, uint32_t pass_spp, uint32_t max_spp, uint32_t rank,
+                                  void* stream) {
+    return adaptive_select(width, height, d_workspace, workspace_bytes, threshold, eps, pass_spp, max_spp,
+                           rank > 255 ? 256 : (int)rank, stream);
 }
 
 int rt_adaptive_resolve_async(const rt_render_params* p, const void* d_workspace, uint64_t workspace_bytes,
@@ -1195,12 +1244,14 @@ int rt_adaptive_resolve_async(const rt_render_params* p, const void* d_workspace
     return RT_OK;
 }
 
-int rt_render_adaptive(rt_scene* s, const rt_render_params* p, const rt_adaptive_params* a, double* out_mean_rgb,
-                       double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats) {
+// the loop of rt_render_adaptive (rank < 0) and rt_render_adaptive_rank
+static int render_adaptive(rt_scene* s, const rt_render_params* p, const rt_adaptive_params* a, int rank,
+                           double* out_mean_rgb, double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats) {
     const auto t0 = std::chrono::steady_clock::now();
     int rc = check_params(p);
     if (rc || (rc = check_moments_flags(p))) return rc;
     if (!s || !a || !out_mean_rgb || !out_sq_rgb) return set_error(RT_ERR_INVALID, "scene/adaptive params/output is NULL");
+    if (rank > 255) return set_error(RT_ERR_INVALID, "rank must be 0..255");
     if (a->pass_spp < 2 || a->max_spp < a->pass_spp || a->max_spp % a->pass_spp)
         return set_error(RT_ERR_INVALID, "pass_spp must be >= 2 and max_spp a multiple of it");
     if (!(a->threshold >= 0.0) || !(a->eps >= 0.0) || !std::isfinite(a->eps))
@@ -1230,8 +1281,8 @@ int rt_render_adaptive(rt_scene* s, const rt_render_params* p, const rt_adaptive
     for (uint32_t base = 0; base < a->max_spp; base += a->pass_spp) {
         if ((rc = rt_adaptive_pass_async(s, &pass, s->adaptive, L.bytes, base != 0, n_list, base, nullptr))) return rc;
         if (base + a->pass_spp >= a->max_spp) break;  // the cap: nothing could be selected
-        if ((rc = rt_adaptive_select_async(p->width, p->height, s->adaptive, L.bytes, a->threshold, a->eps, a->pass_spp,
-                                           a->max_spp, nullptr)))
+        if ((rc = adaptive_select(p->width, p->height, s->adaptive, L.bytes, a->threshold, a->eps, a->pass_spp, a->max_spp,
+                                  rank, nullptr)))
             return rc;
         HIP_TRY(hipMemcpy(&n_list, (char*)s->adaptive + L.info, sizeof(n_list), hipMemcpyDeviceToHost));
         if (n_list == 0) break;
@@ -1253,6 +1304,16 @@ int rt_render_adaptive(rt_scene* s, const rt_render_params* p, const rt_adaptive
         opt_stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return RT_OK;
+}
+
+int rt_render_adaptive(rt_scene* s, const rt_render_params* p, const rt_adaptive_params* a, double* out_mean_rgb,
+                       double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats) {
+    return render_adaptive(s, p, a, -1, out_mean_rgb, out_sq_rgb, out_count, opt_stats);
+}
+
+int rt_render_adaptive_rank(rt_scene* s, const rt_render_params* p, const rt_adaptive_params* a, uint32_t rank,
+                            double* out_mean_rgb, double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats) {
+    return render_adaptive(s, p, a, rank > 255 ? 256 : (int)rank, out_mean_rgb, out_sq_rgb, out_count, opt_stats);
 }
 
 int rt_intersect_rays(rt_scene* s, const double* rays, uint32_t n, rt_hit* out) {

@@ -3,6 +3,7 @@
 //
 //   dn_camera_rays  camera_dir's arithmetic (render.hip) at the pixel centres
 //   dn_prepare      mean, second moment, rays and first hits -> the working records
+//   dn_prepare_counts  the same with every pixel's own sample count (rt_denoise_counts_async)
 //   dn_atrous       one iteration of the filter, launched once per step s = 2^i
 //
 // Working records, 96 B a pixel in the caller's workspace: two colour buffers of
@@ -136,6 +137,63 @@ __global__ __launch_bounds__(kThreads) void dn_prepare(const double* __restrict_
     }
     const double var = ((kLr * kLr) * v[0] + (kLg * kLg) * v[1]) + (kLb * kLb) * v[2];
     const bool ok = finite(m[0]) && finite(m[1]) && finite(m[2]) && finite(var);
+    colour[2 * pix] = make_double2(m[0], m[1]);
+    colour[2 * pix + 1] = make_double2(m[2], ok ? var : __longlong_as_double((long long)kNotOk));
+    if (out_var) out_var[pix] = var;
+    // rt_hit as 8 doubles: t, geometry_normal, shading_normal, {inside, prim}
+    const double* h = s_hit + 9 * l;
+    const double* r = s_ray + 7 * l;
+    const double t = h[0];
+    const bool hit = (int32_t)(__double_as_longlong(h[7]) >> 32) != RT_HIT_MISS;
+    uint4 a, b;
+    a.x = __float_as_uint((float)h[4]);
+    a.y = __float_as_uint((float)h[5]);
+    a.z = __float_as_uint((float)h[6]);
+    a.w = __float_as_uint((float)t);
+    b.x = __float_as_uint((float)(r[0] + t * r[3]));
+    b.y = __float_as_uint((float)(r[1] + t * r[4]));
+    b.z = __float_as_uint((float)(r[2] + t * r[5]));
+    b.w = (hit ? kHit : 0u) | (ok ? kOk : 0u);
+    guide[2 * pix] = a;
+    guide[2 * pix + 1] = b;
+}
+
+// dn_prepare with the pixel's own sample count in place of the frame's (rt_denoise_counts_async):
+// denom is count - 1, and a pixel with fewer than two samples is not ok.  The rest is dn_prepare's,
+// restated: shared through a function, dn_prepare itself compiles to other registers, and that
+// kernel stays as it was.  Lane l needs the count of pixel l and of no other, so the block's
+// 1 KiB of counts is one 4-byte load a lane, whole lines a wave, started before the staging
+// loops so that it is in flight with them; a trip through LDS would add a store and a load
+// and move the same bytes.
+__global__ __launch_bounds__(kThreads) void dn_prepare_counts(const double* __restrict__ mean,
+                                                              const double* __restrict__ sq,
+                                                              const double* __restrict__ rays,
+                                                              const double* __restrict__ hits,
+                                                              const uint32_t* __restrict__ count, uint64_t n,
+                                                              double2* __restrict__ colour, uint4* __restrict__ guide,
+                                                              double* __restrict__ out_var) {
+    __shared__ double s_mean[staged_doubles<3>()], s_sq[staged_doubles<3>()];
+    __shared__ double s_ray[staged_doubles<6>()], s_hit[staged_doubles<8>()];
+    const uint64_t own = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t cnt = own < n ? count[own] : 0u;
+    const double denom = (double)cnt - 1.0;
+    stage_records<3>(s_mean, mean, n * 3);
+    stage_records<3>(s_sq, sq, n * 3);
+    stage_records<6>(s_ray, rays, n * 6);
+    stage_records<8>(s_hit, hits, n * 8);
+    __syncthreads();
+    const uint32_t l = threadIdx.x;
+    const uint64_t pix = (uint64_t)blockIdx.x * kThreads + l;
+    if (pix >= n) return;
+    double m[3], v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        m[c] = s_mean[3 * l + c];
+        const double d = s_sq[3 * l + c] - m[c] * m[c];  // below 0 by rounding only: clamped; a NaN stays
+        v[c] = (d < 0.0 ? 0.0 : d) / denom;
+    }
+    const double var = ((kLr * kLr) * v[0] + (kLg * kLg) * v[1]) + (kLb * kLb) * v[2];
+    const bool ok = cnt >= 2 && finite(m[0]) && finite(m[1]) && finite(m[2]) && finite(var);
     colour[2 * pix] = make_double2(m[0], m[1]);
     colour[2 * pix + 1] = make_double2(m[2], ok ? var : __longlong_as_double((long long)kNotOk));
     if (out_var) out_var[pix] = var;
@@ -304,12 +362,18 @@ hipError_t launch_camera_rays(const KParams& k, double* rays, hipStream_t st) {
 uint64_t denoise_buffer_bytes(uint64_t n_pixels) { return (n_pixels * 32 + 255) / 256 * 256; }
 
 hipError_t launch_denoise(const DenoiseSettings& S, const double* mean, const double* sq, const double* rays,
-                          const rt_hit* hits, double* out, double* out_var, void* workspace, hipStream_t st) {
+                          const rt_hit* hits, double* out, double* out_var, void* workspace, hipStream_t st,
+                          const uint32_t* count) {
     const uint64_t n = (uint64_t)S.width * S.height, buf = denoise_buffer_bytes(n);
     double2* colour[2] = {(double2*)workspace, (double2*)((char*)workspace + buf)};
     uint4* guide = (uint4*)((char*)workspace + 2 * buf);
-    hipLaunchKernelGGL(dn_prepare, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, mean, sq,
-                       rays, (const double*)hits, n, (double)S.spp - 1.0, colour[0], guide, out_var);
+    const dim3 blocks((unsigned)((n + kThreads - 1) / kThreads));
+    if (count)
+        hipLaunchKernelGGL(dn_prepare_counts, blocks, dim3(kThreads), 0, st, mean, sq, rays, (const double*)hits, count,
+                           n, colour[0], guide, out_var);
+    else
+        hipLaunchKernelGGL(dn_prepare, blocks, dim3(kThreads), 0, st, mean, sq, rays, (const double*)hits, n,
+                           (double)S.spp - 1.0, colour[0], guide, out_var);
     hipError_t e = hipGetLastError();
     for (uint32_t i = 0; i < S.iterations && e == hipSuccess; ++i) {
         DnFilter P;

@@ -3,6 +3,7 @@
 //
 //   se_kernel       se = sqrt(max(m2 - mean * mean, 0) / (spp - 1)) per value, and per block
 //                   one partial of the summary
+//   se_counts_kernel  the same with (count of the value's pixel - 1) for (spp - 1)
 //   se_fold_kernel  the partials, in block order, to the 8 doubles of the summary
 //
 // The arrays are [n_pixels][3] f64, interleaved.  A pixel is 24 bytes, so no 16-byte word
@@ -128,6 +129,93 @@ __global__ __launch_bounds__(kSeThreads) void se_kernel(const double2* __restric
     }
 }
 
+// se_kernel where every pixel has a sample count of its own (rt_error_estimate_counts_async): a
+// value's denom and `one` come from its pixel's count.  The map, the flags and the fold are
+// se_kernel's, restated line for line: shared through a function, se_kernel's own instructions
+// come out in another order, and that kernel stays as it was compiled.  A wave's trip is 128
+// whole pixels, 512 contiguous bytes of counts: the wave loads them as two coalesced 4-byte
+// loads a lane (the array is only 4-byte aligned) into LDS, and a lane reads the count of each
+// of its six values from there (neighbouring lanes read the same or the next word: no bank
+// conflicts).  The counts are staged one trip ahead, into the buffer the flags' parity names,
+// so the trip's one barrier orders them too and their load overlaps the trip's other loads;
+// only the first trip pays a barrier of its own.
+__global__ __launch_bounds__(kSeThreads) void se_counts_kernel(const double2* __restrict__ mean,
+                                                               const double2* __restrict__ sq,
+                                                               const uint32_t* __restrict__ count, uint64_t n_vals,
+                                                               uint64_t trips, double2* __restrict__ se,
+                                                               double* __restrict__ part) {
+    // a value's flag: se or mean not finite; two buffers, so one barrier a trip is enough
+    __shared__ uint16_t s_bad[2][kSeWaves][kSeVals / 2];
+    __shared__ uint32_t s_cnt[2][kSeWaves][kSeVals / 3];
+    __shared__ double s_red[kSeWaves][8];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    double a_se[3] = {0.0, 0.0, 0.0}, a_mean[3] = {0.0, 0.0, 0.0}, a_max = 0.0, a_bad = 0.0;
+    const auto stage_counts = [&](uint64_t t) {
+        const uint64_t p0 = ((blockIdx.x * trips + t) * kSeWaves + wave) * (kSeVals / 3);  // the wave's first pixel
+#pragma unroll
+        for (uint32_t k = 0; k < kSeVals / 3 / 64; ++k) {
+            const uint64_t p = p0 + 64 * k + lane;
+            s_cnt[t & 1][wave][64 * k + lane] = p < n_vals / 3 ? count[p] : 0u;
+        }
+    };
+    stage_counts(0);
+    __syncthreads();
+    for (uint64_t t = 0; t < trips; ++t) {
+        const uint64_t v0 = ((blockIdx.x * trips + t) * kSeWaves + wave) * kSeVals;  // the wave's first value
+        uint16_t* bad = s_bad[t & 1][wave];
+        if (t + 1 < trips) stage_counts(t + 1);
+        double m[2 * kSeWords], e[2 * kSeWords];
+#pragma unroll
+        for (uint32_t k = 0; k < kSeWords; ++k) {
+            const uint64_t v = v0 + 2 * (64 * k + lane);
+            double2 a = make_double2(0.0, 0.0), q = a;
+            if (v + 1 < n_vals) {
+                a = mean[v / 2]; q = sq[v / 2];
+            } else if (v < n_vals) {  // the last value of an odd count
+                a.x = ((const double*)mean)[v]; q.x = ((const double*)sq)[v];
+            }
+            const uint32_t x = 2 * (64 * k + lane);  // the word's first value within the trip
+            const uint32_t c0 = s_cnt[t & 1][wave][x / 3], c1 = s_cnt[t & 1][wave][(x + 1) / 3];
+            const double2 r = make_double2(se_of(a.x, q.x, (double)c0 - 1.0, c0 < 2), se_of(a.y, q.y, (double)c1 - 1.0, c1 < 2));
+            if (se && v + 1 < n_vals) se[v / 2] = r;
+            else if (se && v < n_vals) ((double*)se)[v] = r.x;
+            bad[64 * k + lane] = (uint16_t)((finite(r.x) && finite(a.x) ? 0u : 1u) | (finite(r.y) && finite(a.y) ? 0u : 0x100u));
+            m[2 * k] = a.x; m[2 * k + 1] = a.y; e[2 * k] = r.x; e[2 * k + 1] = r.y;
+        }
+        __syncthreads();
+        const uint8_t* flag = (const uint8_t*)bad;
+#pragma unroll
+        for (uint32_t i = 0; i < 2 * kSeWords; ++i) {
+            const uint32_t x = 2 * (64 * (i / 2) + lane) + (i & 1u), p = x / 3 * 3;  // p: the pixel's first value
+            if (v0 + x >= n_vals) continue;
+            if (flag[p] | flag[p + 1] | flag[p + 2]) {
+                if (x == p) a_bad += 1.0;  // counted once, by the lane of its first value
+            } else {
+                a_se[i % 3] += e[i]; a_mean[i % 3] += m[i];
+                a_max = fmax(a_max, e[i]);
+            }
+        }
+    }
+    // accumulator r holds channel (c0 + r) % 3
+    const uint32_t c0 = 2 * lane % 3;
+    double v[8];
+    v[0] = a_bad; v[7] = a_max;
+#pragma unroll
+    for (uint32_t c = 0; c < 3; ++c) {
+        v[1 + c] = c0 == 0 ? a_se[c] : (c0 == 1 ? a_se[(c + 2) % 3] : a_se[(c + 1) % 3]);
+        v[4 + c] = c0 == 0 ? a_mean[c] : (c0 == 1 ? a_mean[(c + 2) % 3] : a_mean[(c + 1) % 3]);
+    }
+    wave_join(v);
+    if (lane == 0)
+        for (int i = 0; i < 8; ++i) s_red[wave][i] = v[i];
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        double r = s_red[0][threadIdx.x];
+        for (uint32_t w = 1; w < kSeWaves; ++w) r = se_join((int)threadIdx.x, r, s_red[w][threadIdx.x]);
+        part[(uint64_t)blockIdx.x * 8 + threadIdx.x] = r;
+    }
+}
+
 // One block of 8 waves, wave i for summary value i; n_blocks == 0 gives the empty frame's zeros.
 __global__ __launch_bounds__(512) void se_fold_kernel(const double* __restrict__ part, uint32_t n_blocks,
                                                       double* __restrict__ summary) {
@@ -144,13 +232,17 @@ __global__ __launch_bounds__(512) void se_fold_kernel(const double* __restrict__
 }  // namespace
 
 hipError_t launch_error_estimate(const double* mean, const double* sq, uint64_t n_pixels, uint32_t spp, double* se,
-                                 double* summary, double* part, hipStream_t st) {
+                                 double* summary, double* part, hipStream_t st, const uint32_t* count) {
     const uint64_t n_vals = n_pixels * 3, tiles = (n_vals + kSeVals - 1) / kSeVals;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kSeMaxBlocks, (tiles + kSeWaves - 1) / kSeWaves);
     if (blocks) {
         const uint64_t trips = (tiles + (uint64_t)blocks * kSeWaves - 1) / ((uint64_t)blocks * kSeWaves);
-        hipLaunchKernelGGL(se_kernel, dim3(blocks), dim3(kSeThreads), 0, st, (const double2*)mean, (const double2*)sq,
-                           n_vals, trips, (double)spp - 1.0, spp == 1 ? 1 : 0, (double2*)se, part);
+        if (count)
+            hipLaunchKernelGGL(se_counts_kernel, dim3(blocks), dim3(kSeThreads), 0, st, (const double2*)mean,
+                               (const double2*)sq, count, n_vals, trips, (double2*)se, part);
+        else
+            hipLaunchKernelGGL(se_kernel, dim3(blocks), dim3(kSeThreads), 0, st, (const double2*)mean, (const double2*)sq,
+                               n_vals, trips, (double)spp - 1.0, spp == 1 ? 1 : 0, (double2*)se, part);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

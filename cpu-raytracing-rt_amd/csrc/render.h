@@ -189,6 +189,9 @@ hipError_t launch_adaptive_accumulate(void* ws, uint64_t n_tiles, const double* 
                                       bool first, hipStream_t st);
 hipError_t launch_adaptive_select(void* ws, uint64_t n_tiles, double threshold, double eps, uint32_t pass_spp,
                                   uint32_t max_spp, hipStream_t st);
+// the same with the ranked tile error (as_metric_rank); rank 0..255
+hipError_t launch_adaptive_select_rank(void* ws, uint32_t W, uint32_t H, double threshold, double eps,
+                                       uint32_t pass_spp, uint32_t max_spp, uint32_t rank, hipStream_t st);
 hipError_t launch_adaptive_resolve(const void* ws, uint32_t W, uint32_t H, double* mean, double* sq, uint32_t* count,
                                    hipStream_t st);
 // compact: 0 the f64 triangle layout, 1 the compact one, 2 its pair lines (when the scene has them)
@@ -212,9 +215,10 @@ hipError_t launch_unpack(const double* g, double* img, uint32_t W, uint32_t H, u
                          uint32_t per_rank, hipStream_t st);
 // moments.hip: (mean, second moment, spp) -> standard error of the mean per value and the
 // frame summary (rt_error_estimate_async); part: kSeMaxBlocks * 8 doubles of scratch
+// count: nullptr, or [n_pixels] u32, every pixel's own count in place of spp (rt_error_estimate_counts_async)
 constexpr uint32_t kSeMaxBlocks = 1024;
 hipError_t launch_error_estimate(const double* mean, const double* sq, uint64_t n_pixels, uint32_t spp, double* se,
-                                 double* summary, double* part, hipStream_t st);
+                                 double* summary, double* part, hipStream_t st, const uint32_t* count = nullptr);
 // denoise.hip: pixel-centre camera rays [W*H][6] (rt_camera_rays_async), and the à-trous filter
 // (rt_denoise_async) with rt_denoise_params' defaults resolved (squarings: the count itself).
 // workspace: three buffers of denoise_buffer_bytes(W * H), colour, colour, guide.
@@ -226,7 +230,8 @@ struct DenoiseSettings {
 hipError_t launch_camera_rays(const KParams& k, double* rays, hipStream_t st);
 uint64_t denoise_buffer_bytes(uint64_t n_pixels);
 hipError_t launch_denoise(const DenoiseSettings& S, const double* mean, const double* sq, const double* rays,
-                          const rt_hit* hits, double* out, double* out_var, void* workspace, hipStream_t st);
+                          const rt_hit* hits, double* out, double* out_var, void* workspace, hipStream_t st,
+                          const uint32_t* count = nullptr);  // count: [H][W] u32 in place of S.spp (rt_denoise_counts_async)
 // ellipsoid records: aux = dev_rcp(radii), the device's own reciprocals (rt_device.h)
 hipError_t launch_ell_rcp(DevShape* shapes, uint32_t n, hipStream_t st);
 // checksum_kernel: order-free content hash of a device array (rt_scene_checksum)

@@ -354,6 +354,14 @@ int rt_render_tiles_moments_async(rt_scene* scene, const rt_render_params* param
    Scratch comes from a small per-device pool that orders its users across streams. */
 int rt_error_estimate_async(const double* d_mean, const double* d_sq, uint64_t n_pixels, uint32_t spp,
                             double* d_se, double* d_summary, void* hip_stream);
+/* rt_error_estimate_async for a frame whose pixels have counts of their own
+   (rt_adaptive_resolve_async's d_count): d_count [n_pixels] u32, required, 4-byte aligned.
+   Per value se = sqrt(max(sq - mean * mean, 0) / (count_pixel - 1)); count_pixel < 2 is the
+   spp == 1 rule, +inf (NaN where an input is NaN), so such a pixel counts in summary [0].
+   The summary, its fixed order (the same function of n_pixels), the scratch pool and the
+   stream ordering are rt_error_estimate_async's: a uniform count c gives the bytes of spp = c. */
+int rt_error_estimate_counts_async(const double* d_mean, const double* d_sq, const uint32_t* d_count,
+                                   uint64_t n_pixels, double* d_se, double* d_summary, void* hip_stream);
 
 /* ---- denoiser: a variance-guided a-trous filter (no counterpart in the reference) ----
    The first consumer of the second moment: it smooths where the estimate is uncertain,
@@ -419,6 +427,17 @@ int rt_denoise_async(const rt_denoise_params* p, const double* d_mean, const dou
                      const double* d_rays, const rt_hit* d_hits,
                      double* d_out, double* d_out_var /* NULL ok */,
                      void* d_workspace, uint64_t workspace_bytes, void* hip_stream);
+/* rt_denoise_async for a frame whose pixels have counts of their own: d_count [H][W] u32,
+   required, 4-byte aligned (rt_adaptive_resolve_async's d_count).  p->spp is ignored, any
+   value is accepted.  Preparation: v_c = max(sq_c - mean_c * mean_c, 0) / (count - 1) with the
+   pixel's count, and ok = count >= 2 && the three mean_c and var all finite, so a pixel with
+   too few samples is filled from its neighbours like any other missing pixel.  The filter is
+   unchanged: the per-pixel var already carries the count.  RT_ERR_INVALID as
+   rt_denoise_async (but for spp), and a d_count that is NULL or overlaps an output. */
+int rt_denoise_counts_async(const rt_denoise_params* p, const double* d_mean, const double* d_sq,
+                            const uint32_t* d_count, const double* d_rays, const rt_hit* d_hits,
+                            double* d_out, double* d_out_var /* NULL ok */,
+                            void* d_workspace, uint64_t workspace_bytes, void* hip_stream);
 
 /* ---- adaptive sampling: error-driven passes over a device-built tile list ----
    A frame is rendered in passes of pass_spp samples.  The first pass covers every 16x16 tile;
@@ -480,9 +499,24 @@ int rt_adaptive_pass_async(rt_scene* scene, const rt_render_params* params, void
    or NaN, eps negative or not finite, the workspace as above. */
 int rt_adaptive_select_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
                              double threshold, double eps, uint32_t pass_spp, uint32_t max_spp, void* hip_stream);
+/* rt_adaptive_select_async in every respect (workspace checks, tiles at the cap, count < 2,
+   tile_flag, the list, info, the error codes) except the value written to tile_err, which is
+   ranked: one pixel that a rare path lit (e ~ 1 at any count) no longer holds its tile open.
+   For each of the tile's 256 packed pixels, e as above and g = e when e is finite and > 0,
+   else 0 (pixels outside the image have zero accumulators: g = 0; a non-finite e flags the
+   tile as before).  With m the tile's pixels inside the image (from its index, width and
+   height) and r = rank * m / 256 in integer arithmetic, so that a ragged tile is not measured
+   by a pixel it does not have, tile_err is the (r + 1)-th largest of the 256 values g, counted
+   with multiplicity: one of the inputs, unchanged (finite doubles >= 0 order as their bit
+   patterns).  rank 0 is rt_adaptive_select_async's maximum, bit for bit; rank 12 is about the
+   95th percentile of a full tile.  RT_ERR_INVALID also for rank > 255. */
+int rt_adaptive_select_rank_async(uint32_t width, uint32_t height, void* d_workspace, uint64_t workspace_bytes,
+                                  double threshold, double eps, uint32_t pass_spp, uint32_t max_spp,
+                                  uint32_t rank /* 0..255 */, void* hip_stream);
 /* The frame from the state: d_mean, d_sq [H][W][3] f64 = acc / tile_count, d_count NULL or
    [H][W] u32.  d_mean is ready for rt_tonemap_bytes_async; (d_mean, d_sq) are what
-   rt_error_estimate_async and rt_denoise_async take only when the count is uniform. */
+   rt_error_estimate_async and rt_denoise_async take only when the count is uniform;
+   with d_count they are what rt_error_estimate_counts_async and rt_denoise_counts_async take. */
 int rt_adaptive_resolve_async(const rt_render_params* params, const void* d_workspace, uint64_t workspace_bytes,
                               double* d_mean, double* d_sq, uint32_t* d_count /* NULL ok */, void* hip_stream);
 /* The loop on the host: a pass over all tiles at base 0; select; read info (16 bytes); a pass
@@ -493,6 +527,10 @@ int rt_adaptive_resolve_async(const rt_render_params* params, const void* d_work
    read-backs included), total_ms; the other counters 0. */
 int rt_render_adaptive(rt_scene* scene, const rt_render_params* params, const rt_adaptive_params* adaptive,
                        double* out_mean_rgb, double* out_sq_rgb, uint32_t* out_count, rt_stats* opt_stats);
+/* The same loop with rt_adaptive_select_rank_async as its select; rank > 255: RT_ERR_INVALID. */
+int rt_render_adaptive_rank(rt_scene* scene, const rt_render_params* params, const rt_adaptive_params* adaptive,
+                            uint32_t rank, double* out_mean_rgb, double* out_sq_rgb, uint32_t* out_count,
+                            rt_stats* opt_stats);
 
 /* Diagnostics: the scene's raw device counter words (n <= 64), accumulated by
    RT_FLAG_STATS renders: words 0..9 are rt_stats' counters; word 10 counts the

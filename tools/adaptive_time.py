@@ -1,8 +1,8 @@
 """Device-event times of the adaptive-sampling calls (DESIGN.md §4 "Adaptive sampling").
 
-    python tools/adaptive_time.py pipeline [--sizes 1920x1080,3840x2160]
+    python tools/adaptive_time.py pipeline [--sizes 1920x1080,3840x2160] [--rank 12]
     python tools/adaptive_time.py form [--workloads C2,C3] [--spp 32]
-    python tools/adaptive_time.py frame [--workload C2] [--pass-spp 32] [--max-spp 256] [--threshold 0.05]
+    python tools/adaptive_time.py frame [--workload C2] [--pass-spp 32] [--max-spp 256] [--threshold 0.05] [--rank 12]
 
 pipeline: rt_adaptive_select_async and rt_adaptive_resolve_async on synthetic state, the median of
   --calls calls after two warm-up calls, with the bytes they have to move.  as_accumulate has no
@@ -78,6 +78,17 @@ def pipeline(a):
         sq, count = torch.empty_like(mean), torch.empty((h, w), dtype=torch.int32, device="cuda")
         stream = torch.cuda.current_stream().cuda_stream
         sel = timed(lambda: rt.adaptive_select_async(w, h, ws.data_ptr(), ws.numel(), 0.05, 0.0, 16, 256, stream), a.calls)
+        if a.rank is not None:  # plain and ranked select alternating, call by call
+            plain, ranked = [], []
+            for call in range(a.calls + 2):
+                t = (timed(lambda: rt.adaptive_select_async(w, h, ws.data_ptr(), ws.numel(), 0.05, 0.0, 16, 256, stream), 1, 0)[0],
+                     timed(lambda: rt.adaptive_select_rank_async(w, h, ws.data_ptr(), ws.numel(), 0.05, 0.0, 16, 256, a.rank,
+                                                                 stream), 1, 0)[0])
+                if call >= 2:
+                    plain.append(t[0])
+                    ranked.append(t[1])
+            print(f"{size}, {n} tiles, alternating: select {spread(plain)}; select at rank {a.rank} {spread(ranked)}; "
+                  f"ratio of medians {statistics.median(ranked) / statistics.median(plain):.2f}")
         res = timed(lambda: rt.adaptive_resolve_async(p, ws.data_ptr(), ws.numel(), mean.data_ptr(), sq.data_ptr(),
                                                       count.data_ptr(), stream), a.calls)
         b_sel, b_res = n * (12288 + 4 + 12) + n * 16, n * (12288 + 4) + w * h * 52
@@ -108,29 +119,29 @@ def frame(a):
     scene, params = load(a.workload, a.max_spp)
     w, h = params.width, params.height
     ws, lay = workspace(w, h)
-    big = 2 ** 32 - 1
+    big, rank = 2 ** 32 - 1, a.rank or 0  # rank 0 is the plain select, bit for bit
 
     def max_err():
-        rt.adaptive_select_async(w, h, ws.data_ptr(), ws.numel(), a.threshold, 0.0, a.pass_spp, big)
+        rt.adaptive_select_rank_async(w, h, ws.data_ptr(), ws.numel(), a.threshold, 0.0, a.pass_spp, big, rank)
         torch.cuda.synchronize()
         raw = ws[lay["info"]:lay["info"] + 16].cpu().numpy()
         return float(raw[8:].view(np.float64)[0]), int(raw[4:8].view(np.uint32)[0])
 
     for rep in range(a.calls):
-        mean, sq, count, info = scene.render_adaptive(params, a.pass_spp, a.max_spp, a.threshold)
+        mean, sq, count, info = scene.render_adaptive(params, a.pass_spp, a.max_spp, a.threshold, rank=rank)
         fixed = timed(lambda: scene.adaptive_pass_async(params, ws.data_ptr(), ws.numel(), False, 0, 0), 1, warm=0)
         e_fixed = max_err()
         base, n_list = 0, 0
         while base < a.max_spp:  # the driver's loop once more, to measure its final state
             scene.adaptive_pass_async(params.replace(spp=a.pass_spp), ws.data_ptr(), ws.numel(), base != 0, n_list, base)
-            rt.adaptive_select_async(w, h, ws.data_ptr(), ws.numel(), a.threshold, 0.0, a.pass_spp, a.max_spp)
+            rt.adaptive_select_rank_async(w, h, ws.data_ptr(), ws.numel(), a.threshold, 0.0, a.pass_spp, a.max_spp, rank)
             torch.cuda.synchronize()
             n_list, base = int(ws[lay["info"]:lay["info"] + 4].cpu().numpy().view(np.uint32)[0]), base + a.pass_spp
             if n_list == 0:
                 break
         e_adaptive = max_err()
         hist = {int(k): int(v) for k, v in zip(*np.unique(count, return_counts=True))}
-        print(f"{a.workload} {w}x{h}, passes of {a.pass_spp} to {a.max_spp}, threshold {a.threshold}: adaptive "
+        print(f"{a.workload} {w}x{h}, passes of {a.pass_spp} to {a.max_spp}, threshold {a.threshold}, rank {rank}: adaptive "
               f"{info['paths']} samples ({info['paths'] / (w * h * a.max_spp):.3f} of the fixed frame's), kernel "
               f"{info['kernel_ms']:.2f} ms, largest tile error {e_adaptive[0]:.4f} ({e_adaptive[1]} flagged); fixed "
               f"{a.max_spp} spp pass {fixed[0]:.2f} ms, largest tile error {e_fixed[0]:.4f}; pixels by count {hist}")
@@ -147,6 +158,7 @@ def main():
     ap.add_argument("--max-spp", type=int, default=256)
     ap.add_argument("--threshold", type=float, default=0.05)
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--rank", type=int, help="pipeline: also time the ranked select; frame: the tile error's rank (0..255)")
     a = ap.parse_args()
     dict(pipeline=pipeline, form=form, frame=frame)[a.mode](a)
 

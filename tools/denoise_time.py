@@ -1,6 +1,8 @@
 """Device-event times of rt_denoise_async on synthetic full-size frames.
 
     python tools/denoise_time.py [--sizes 1920x1080,3840x2160] [--calls 9]
+    python tools/denoise_time.py --counts      rt_error_estimate_counts_async and rt_denoise_counts_async
+                                               against the plain entries, alternating
 
 Per size: the whole call at the default 5 iterations, and the call at 1..5 iterations, whose
 differences are the times of the iterations with s = 2, 4, 8, 16 (the call at 1 iteration is
@@ -71,6 +73,52 @@ def trace_summary(root):
               ", ".join(f"{n} {statistics.median(c[i] for c in runs):.1f} us" for i, n in enumerate(names)))
 
 
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def counts_leg(a):
+    """The counts entries against the plain ones, alternating call by call: the standard error (with
+    its se output), and the denoiser at one iteration, whose difference is dn_prepare_counts against
+    dn_prepare (the s = 1 launch is the same kernel on the same records)."""
+    for size in a.sizes.split(","):
+        w, h = map(int, size.split("x"))
+        n = w * h
+        mean, sq, rays, hits = frame(w, h)
+        count = torch.full((h, w), 16, dtype=torch.int32, device="cuda")
+        out, var = torch.empty((h, w, 3), dtype=torch.float64, device="cuda"), torch.empty((h, w), dtype=torch.float64, device="cuda")
+        se, summary = torch.empty_like(mean), torch.empty(8, dtype=torch.float64, device="cuda")
+        ws = torch.empty(rt.denoise_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        p = rt.rt_denoise_params(width=w, height=h, spp=16, iterations=1)
+        tail = (rays.data_ptr(), hits.data_ptr(), out.data_ptr(), var.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        legs = {
+            "se plain": lambda: rt.error_estimate_async(mean.data_ptr(), sq.data_ptr(), n, 16, se.data_ptr(), summary.data_ptr(), stream),
+            "se counts": lambda: rt.error_estimate_counts_async(mean.data_ptr(), sq.data_ptr(), count.data_ptr(), n, se.data_ptr(),
+                                                                summary.data_ptr(), stream),
+            "denoise(1) plain": lambda: rt.denoise_async(p, mean.data_ptr(), sq.data_ptr(), *tail),
+            "denoise(1) counts": lambda: rt.denoise_counts_async(p, mean.data_ptr(), sq.data_ptr(), count.data_ptr(), *tail),
+        }
+        ms = {k: [] for k in legs}
+        for call in range(a.calls + 2):  # plain, counts, plain, counts, ...; two warm-up rounds
+            for k, fn in legs.items():
+                t = timed(fn)
+                if call >= 2:
+                    ms[k].append(t)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k, b in (("se plain", 72), ("se counts", 76)):
+            print(f"{size} {k}: {med[k]:.3f} ms (min {min(ms[k]):.3f}, max {max(ms[k]):.3f}), {n * b / 1e6:.1f} MB, "
+                  f"{n * b / med[k] / 1e9:.2f} TB/s")
+        d = med["denoise(1) counts"] - med["denoise(1) plain"]
+        print(f"{size} denoise at 1 iteration: plain {med['denoise(1) plain']:.3f} ms, counts {med['denoise(1) counts']:.3f} ms: "
+              f"dn_prepare_counts - dn_prepare = {d * 1e3:+.1f} us for {n * 4 / 1e6:.1f} MB more on {n * 232 / 1e6:.1f} MB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1920x1080,3840x2160")
@@ -78,9 +126,12 @@ def main():
     ap.add_argument("--only", type=int, default=0, help="time calls of this many iterations only")
     ap.add_argument("--squarings", type=int, default=0, help="normal_squarings (0: the default, 7)")
     ap.add_argument("--trace", help="summarise a kernel trace directory and exit")
+    ap.add_argument("--counts", action="store_true", help="the per-pixel-count entries against the plain ones")
     a = ap.parse_args()
     if a.trace:
         return trace_summary(a.trace)
+    if a.counts:
+        return counts_leg(a)
     for size in a.sizes.split(","):
         w, h = map(int, size.split("x"))
         mean, sq, rays, hits = frame(w, h)
