@@ -46,6 +46,8 @@ RT_HIT_MISS, RT_HIT_NONE = -1, -2
 RT_DENOISE_ITERATIONS, RT_DENOISE_NORMAL_SQUARINGS = 5, 7
 RT_DENOISE_SIGMA_L, RT_DENOISE_SIGMA_Z, RT_DENOISE_EPS = 4.0, 0.01, 1e-8
 RT_DENOISE_SQUARINGS_NONE = 0xFFFFFFFF
+RT_METRICS_F64, RT_METRICS_U8 = 0, 1
+RT_METRICS_EPS = 1e-2
 RT_TILE = 16
 ERRORS = {0: "OK", -1: "INVALID", -2: "DEVICE", -3: "NOMEM", -4: "PARSE", -5: "IO", -6: "UNSUPPORTED"}
 (RT_OK, RT_ERR_INVALID, RT_ERR_DEVICE, RT_ERR_NOMEM, RT_ERR_PARSE, RT_ERR_IO,
@@ -119,6 +121,12 @@ class rt_denoise_params(C.Structure):
                 ("sigma_z", C.c_double), ("eps", C.c_double)]
 
 
+class rt_metrics_params(C.Structure):
+    """Zeroed peak, eps and window take the header's defaults (rt_image_metrics_async)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("_pad", C.c_uint32),
+                ("peak", C.c_double), ("eps", C.c_double), ("window", C.c_double * 11)]
+
+
 class rt_adaptive_layout(C.Structure):
     """Byte offsets of the adaptive workspace's sub-buffers (rt_adaptive_workspace_bytes)."""
     _fields_ = [(k, C.c_uint64) for k in ("n_tiles", "acc_sum", "acc_sq", "tile_count", "tile_err", "tile_flag",
@@ -184,6 +192,10 @@ EXPORTS = {
                                                  C.c_void_p]),
     "rt_denoise_counts_async": (C.c_int, [C.POINTER(rt_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rt_ssim_window": (C.c_int, [C.c_double, C.c_void_p]),
+    "rt_image_metrics_workspace_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "rt_image_metrics_async": (C.c_int, [C.POINTER(rt_metrics_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rt_tiles_per_rank": (C.c_int, [C.POINTER(rt_render_params), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rt_sample_chunks": (C.c_int, [C.POINTER(rt_render_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_render_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
@@ -825,6 +837,67 @@ def denoise_counts_async(p: rt_denoise_params, d_mean_ptr: int, d_sq_ptr: int, d
                                          C.c_void_p(d_count_ptr), C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
                                          C.c_void_p(d_out_ptr), C.c_void_p(d_out_var_ptr), C.c_void_p(d_workspace_ptr),
                                          workspace_bytes, C.c_void_p(stream_ptr)))
+
+
+def ssim_window(sigma: float = 1.5) -> np.ndarray:
+    """The eleven normalised Gaussian SSIM taps (rt_ssim_window; host only)."""
+    out = np.zeros(11)
+    _check(lib().rt_ssim_window(sigma, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def image_metrics_workspace_bytes(width: int, height: int) -> int:
+    n = C.c_uint64()
+    _check(lib().rt_image_metrics_workspace_bytes(width, height, C.byref(n)))
+    return n.value
+
+
+def image_metrics_async(p: rt_metrics_params, d_a_ptr: int, d_b_ptr: int, d_rel_ptr: int, d_ssim_ptr: int,
+                        d_summary_ptr: int, d_workspace_ptr: int, workspace_bytes: int, stream_ptr: int = 0):
+    """Device frames a (under test) and b (reference), [H][W][3] in p.format -> the 8 doubles of the summary and
+    (pointers 0: none) the per-pixel rel [H][W] and per-window ssim [H - 10][W - 10] (rt_image_metrics_async)."""
+    _check(lib().rt_image_metrics_async(C.byref(p), C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), C.c_void_p(d_rel_ptr),
+                                        C.c_void_p(d_ssim_ptr), C.c_void_p(d_summary_ptr), C.c_void_p(d_workspace_ptr),
+                                        workspace_bytes, C.c_void_p(stream_ptr)))
+
+
+def image_metrics(a: np.ndarray, b: np.ndarray, peak: Optional[float] = None, eps: Optional[float] = None,
+                  window: Optional[np.ndarray] = None, maps: bool = False) -> dict:
+    """The distance of frame a to the reference frame b, both [H, W, 3] float64 radiance or both uint8
+    display bytes, computed on torch's current device (rt_image_metrics_async).  peak, eps, window: None
+    for the header's defaults.  Returns mse, rel_mse, psnr and max_abs over the good pixels, ssim (the mean
+    over the windows that count), bad_pixels, bad_windows, the raw summary, and with maps=True also rel
+    [H, W] and ssim_map [H - 10, W - 10] (empty when the frame has no window)."""
+    import torch
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != b.dtype or a.dtype not in (np.float64, np.uint8) or a.shape != b.shape or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("a and b must both be [H, W, 3] float64 or both [H, W, 3] uint8")
+    h, w, _ = a.shape
+    u8 = a.dtype == np.uint8
+    p = rt_metrics_params(width=w, height=h, format=RT_METRICS_U8 if u8 else RT_METRICS_F64, peak=peak or 0.0, eps=eps or 0.0)
+    if window is not None:
+        p.window[:] = [float(t) for t in window]
+    ws_bytes = image_metrics_workspace_bytes(w, h)
+    d_a, d_b = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (a, b))
+    dev = dict(dtype=torch.float64, device="cuda")
+    d_summary, d_ws = torch.empty(8, **dev), torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    wh, ww = (h - 10, w - 10) if w >= 11 and h >= 11 else (0, 0)
+    d_rel = torch.empty((h, w), **dev) if maps else None
+    d_ssim = torch.empty((wh, ww), **dev) if maps and wh else None
+    image_metrics_async(p, d_a.data_ptr(), d_b.data_ptr(), d_rel.data_ptr() if maps else 0,
+                        d_ssim.data_ptr() if d_ssim is not None else 0, d_summary.data_ptr(), d_ws.data_ptr(), ws_bytes,
+                        torch.cuda.current_stream().cuda_stream)
+    s = d_summary.cpu().numpy()
+    good = w * h - s[0]
+    pk = peak or (255.0 if u8 else 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse = s[1] / (3.0 * good)
+        out = dict(mse=float(mse), rel_mse=float(s[2] / (3.0 * good)), psnr=float(10.0 * np.log10(pk * pk / mse)),
+                   ssim=float(s[5] / s[4]), max_abs=float(s[3]), bad_pixels=int(s[0]), bad_windows=int(s[7]), summary=s)
+    if maps:
+        out["rel"] = d_rel.cpu().numpy()
+        out["ssim_map"] = d_ssim.cpu().numpy() if d_ssim is not None else np.zeros((wh, ww))
+    return out
 
 
 def adaptive_workspace(width: int, height: int):

@@ -1030,6 +1030,78 @@ int rt_denoise_counts_async(const rt_denoise_params* p, const double* d_mean, co
     return denoise(p, d_mean, d_sq, d_count, true, d_rays, d_hits, d_out, d_out_var, d_workspace, workspace_bytes, stream);
 }
 
+int rt_ssim_window(double sigma, double* out11) {
+    if (!out11) return set_error(RT_ERR_INVALID, "out is NULL");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return set_error(RT_ERR_INVALID, "sigma must be finite and > 0");
+    double sum = 0.0;
+    for (int i = 0; i < 11; ++i) {
+        const double d = (double)(i - 5);
+        out11[i] = std::exp(-(d * d) / (2.0 * (sigma * sigma)));
+        sum = sum + out11[i];
+    }
+    for (int i = 0; i < 11; ++i) out11[i] = out11[i] / sum;
+    return RT_OK;
+}
+
+static int metrics_size(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0) return set_error(RT_ERR_INVALID, "width/height must be > 0");
+    if (width > 65535 || height > 65535) return set_error(RT_ERR_INVALID, "width/height must be <= 65535");
+    return RT_OK;
+}
+
+int rt_image_metrics_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
+    if (!bytes) return set_error(RT_ERR_INVALID, "bytes is NULL");
+    if (int rc = metrics_size(width, height)) return rc;
+    *bytes = (metrics_blocks(width, height) * 64 + 255) / 256 * 256;
+    return RT_OK;
+}
+
+int rt_image_metrics_async(const rt_metrics_params* p, const void* d_a, const void* d_b, double* d_rel, double* d_ssim,
+                           double* d_summary, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    if (!p) return set_error(RT_ERR_INVALID, "params is NULL");
+    if (int rc = metrics_size(p->width, p->height)) return rc;
+    if (p->format != RT_METRICS_F64 && p->format != RT_METRICS_U8)
+        return set_error(RT_ERR_INVALID, "format must be RT_METRICS_F64 or RT_METRICS_U8");
+    MetricsSettings S;
+    S.width = p->width; S.height = p->height; S.format = p->format;
+    if (!(p->peak >= 0.0) || !std::isfinite(p->peak) || !(p->eps >= 0.0) || !std::isfinite(p->eps))
+        return set_error(RT_ERR_INVALID, "peak and eps must be finite and > 0 (0: the default)");
+    S.peak = p->peak == 0.0 ? (p->format == RT_METRICS_F64 ? 1.0 : 255.0) : p->peak;
+    S.eps = p->eps == 0.0 ? RT_METRICS_EPS : p->eps;
+    int zeros = 0;
+    for (int i = 0; i < 11; ++i) {
+        if (!(p->window[i] >= 0.0) || !std::isfinite(p->window[i]))
+            return set_error(RT_ERR_INVALID, "the window's taps must be finite and > 0 (all zero: the default)");
+        zeros += p->window[i] == 0.0;
+        S.window[i] = p->window[i];
+    }
+    if (zeros != 0 && zeros != 11)
+        return set_error(RT_ERR_INVALID, "the window mixes zero and non-zero taps (all zero: the default)");
+    if (zeros == 11) rt_ssim_window(1.5, S.window);
+    if (!d_a || !d_b || !d_summary || !d_workspace) return set_error(RT_ERR_INVALID, "a/b/summary/workspace is NULL");
+    const bool f64 = p->format == RT_METRICS_F64;
+    if ((((uintptr_t)d_a | (uintptr_t)d_b) & (f64 ? 7u : 0u)) ||
+        (((uintptr_t)d_rel | (uintptr_t)d_ssim | (uintptr_t)d_summary | (uintptr_t)d_workspace) & 7u))
+        return set_error(RT_ERR_INVALID, "the f64 buffers and the workspace must be 8-byte aligned");
+    const uint64_t n = (uint64_t)p->width * p->height, need = (metrics_blocks(p->width, p->height) * 64 + 255) / 256 * 256;
+    if (workspace_bytes < need)
+        return set_error(RT_ERR_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
+    const uint64_t windows = p->width >= 11 && p->height >= 11 ? (uint64_t)(p->width - 10) * (p->height - 10) : 0;
+    // an output may overlap neither what the kernels read nor another output
+    struct Range { const void* p; uint64_t bytes; };
+    const Range outs[3] = {{d_rel, d_rel ? n * 8 : 0}, {d_ssim, d_ssim ? windows * 8 : 0}, {d_summary, 64}};
+    const Range ins[5] = {{d_a, n * (f64 ? 24 : 3)}, {d_b, n * (f64 ? 24 : 3)}, {d_workspace, need}, outs[1], outs[2]};
+    for (int o = 0; o < 3; ++o)
+        for (int i = 0; i < 5; ++i) {
+            if (i >= 3 && i - 2 <= o) continue;  // an output against the outputs after it
+            const uintptr_t a = (uintptr_t)outs[o].p, b = (uintptr_t)ins[i].p;
+            if (outs[o].bytes && ins[i].bytes && a < b + ins[i].bytes && b < a + outs[o].bytes)
+                return set_error(RT_ERR_INVALID, "rel/ssim/summary overlaps an input, the workspace or another output");
+        }
+    HIP_TRY(launch_image_metrics(S, d_a, d_b, d_rel, d_ssim, d_summary, (double*)d_workspace, (hipStream_t)stream));
+    return RT_OK;
+}
+
 int rt_read_stats(rt_scene* s, rt_stats* out, int reset) {
     if (!s || !out) return set_error(RT_ERR_INVALID, "scene/out is NULL");
     DEVICE_GUARD(s);

@@ -232,6 +232,16 @@ uint64_t denoise_buffer_bytes(uint64_t n_pixels);
 hipError_t launch_denoise(const DenoiseSettings& S, const double* mean, const double* sq, const double* rays,
                           const rt_hit* hits, double* out, double* out_var, void* workspace, hipStream_t st,
                           const uint32_t* count = nullptr);  // count: [H][W] u32 in place of S.spp (rt_denoise_counts_async)
+// metrics.hip: the distance of frame a to frame b (rt_image_metrics_async) with rt_metrics_params'
+// defaults resolved.  part: metrics_blocks(W, H) * 8 doubles, one partial a 32x16 block of pixels.
+constexpr uint32_t kMetricsCoreW = 32, kMetricsCoreH = 16;
+struct MetricsSettings {
+    uint32_t width, height, format;
+    double peak, eps, window[11];
+};
+uint64_t metrics_blocks(uint32_t width, uint32_t height);
+hipError_t launch_image_metrics(const MetricsSettings& S, const void* a, const void* b, double* rel, double* ssim,
+                                double* summary, double* part, hipStream_t st);
 // ellipsoid records: aux = dev_rcp(radii), the device's own reciprocals (rt_device.h)
 hipError_t launch_ell_rcp(DevShape* shapes, uint32_t n, hipStream_t st);
 // checksum_kernel: order-free content hash of a device array (rt_scene_checksum)

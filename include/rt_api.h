@@ -532,6 +532,64 @@ int rt_render_adaptive_rank(rt_scene* scene, const rt_render_params* params, con
                             uint32_t rank, double* out_mean_rgb, double* out_sq_rgb, uint32_t* out_count,
                             rt_stats* opt_stats);
 
+/* ---- image metrics: the distance of a frame to a reference frame (no counterpart in the reference) ----
+   What judges the quality pipeline above: A is the frame under test, B a converged frame of the
+   same scene, both [H][W][3] in one format.  RT_METRICS_F64: f64 radiance, 8-byte aligned (rows
+   need not be 16-byte aligned).  RT_METRICS_U8: display bytes as rt_tonemap_bytes_async writes
+   them, each widened exactly to f64.  Like the denoiser it is rational arithmetic (+ - * /) in a
+   fixed order, IEEE, nothing fused: the maps are the bits of a float64 restatement on the host
+   (tests/test_gpu_metrics.py).
+   Per pixel, with L = (0.2126, 0.7152, 0.0722), the denoiser's:
+     d_c = a_c - b_c;  se = (d_r*d_r + d_g*d_g) + d_b*d_b;
+     rel = (d_r*d_r / (b_r*b_r + eps) + d_g*d_g / (b_g*b_g + eps)) + d_b*d_b / (b_b*b_b + eps);
+     ya = (L_r*a_r + L_g*a_g) + L_b*a_b, yb likewise;  the pixel is good when its six inputs are finite.
+   SSIM over valid windows only: for 0 <= x <= W - 11 and 0 <= y <= H - 11 there is a window whose
+   top-left pixel is (x, y); a frame with W < 11 or H < 11 has none.  The filter is separable over
+   the five planes q = (ya, yb, ya*ya, yb*yb, ya*yb), with the taps w[0..10]:
+     horizontal  h = w[0]*q(x, r), then h = h + w[i]*q(x + i, r) for i = 1..10;
+     vertical    v = w[0]*h(x, y), then v = v + w[j]*h(x, y + j) for j = 1..10.
+   With ma = v0, mb = v1: sa = v2 - ma*ma, sb = v3 - mb*mb, sab = v4 - ma*mb, none of them clamped;
+   C1 = (0.01*peak)*(0.01*peak), C2 = (0.03*peak)*(0.03*peak);
+     ssim = (((2*ma)*mb + C1) * (2*sab + C2)) / (((ma*ma + mb*mb) + C1) * ((sa + sb) + C2)).
+   A window that touches a non-finite pixel comes out non-finite by this arithmetic alone (the taps
+   are positive: no 0*inf hides one); no flag is carried, a window counts exactly when its ssim is
+   finite.
+   Summary, 8 doubles: [0] the pixels that are not good; over the good pixels [1] the sum of se,
+   [2] the sum of rel, [3] the largest |d_c| (0 without a good pixel); [4] the windows that count,
+   [5] the sum of ssim over them, [6] their smallest ssim (+inf without one), [7] the windows that
+   do not count.  The sums have a fixed order that depends on (W, H) alone and use no
+   floating-point atomics: the same bits on every call and stream.  From it the host derives, with
+   good = W*H - [0]: MSE = [1] / (3*good), relMSE = [2] / (3*good), PSNR = 10*log10(peak*peak / MSE),
+   mean SSIM = [5] / [4]. */
+enum { RT_METRICS_F64 = 0, RT_METRICS_U8 = 1 };
+#define RT_METRICS_EPS 1e-2   /* the customary relMSE floor: a definition, not a tuned number */
+typedef struct rt_metrics_params {
+    uint32_t width, height;
+    uint32_t format;      /* RT_METRICS_F64 | RT_METRICS_U8                                    */
+    uint32_t _pad;
+    double peak;          /* 0 = 1.0 for f64, 255.0 for u8; else finite, > 0                    */
+    double eps;           /* 0 = RT_METRICS_EPS; else finite, > 0                               */
+    double window[11];    /* the 1-D SSIM taps, all finite and > 0; all zero = rt_ssim_window(1.5, .) */
+} rt_metrics_params;
+/* Host only: out[i] = exp(-(i - 5)^2 / (2 * sigma^2)), i = 0..10, divided by their sum taken in
+   index order.  exp runs here and nowhere else: the device receives the eleven numbers.  sigma
+   not finite or <= 0, or out NULL: RT_ERR_INVALID. */
+int rt_ssim_window(double sigma, double* out11);
+/* Bytes of rt_image_metrics_async's workspace: 8 doubles for every 32x16 block of pixels, rounded
+   up to 256 B.  Zero width or height, or one above 65535: RT_ERR_INVALID. */
+int rt_image_metrics_workspace_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+/* The metrics above on the current device, stream-ordered, in caller-owned memory: no scene
+   handle and no hidden allocation, as rt_denoise_async.  d_a, d_b [H][W][3] in p->format (they
+   may be the same frame); d_rel NULL or [H][W] f64, the per-pixel rel; d_ssim NULL or
+   [H - 10][W - 10] f64, the per-window ssim (not touched, and NULL is fine, when there is no
+   window); d_summary 8 doubles; f64 buffers and the workspace 8-byte aligned.  RT_ERR_INVALID:
+   zero width or height (or above 65535), an unknown format, a peak, eps or tap that is negative or
+   not finite, a window that mixes zero and non-zero taps, a NULL required pointer, a workspace too
+   small or misaligned, an output overlapping an input, the workspace or another output. */
+int rt_image_metrics_async(const rt_metrics_params* p, const void* d_a, const void* d_b,
+                           double* d_rel /* NULL ok */, double* d_ssim /* NULL ok */, double* d_summary,
+                           void* d_workspace, uint64_t workspace_bytes, void* hip_stream);
+
 /* Diagnostics: the scene's raw device counter words (n <= 64), accumulated by
    RT_FLAG_STATS renders: words 0..9 are rt_stats' counters; word 10 counts the
    last-bounce light queries the timed (no-stats) kernel skips because they cannot
