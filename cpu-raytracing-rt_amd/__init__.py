@@ -48,6 +48,8 @@ RT_DENOISE_SIGMA_L, RT_DENOISE_SIGMA_Z, RT_DENOISE_EPS = 4.0, 0.01, 1e-8
 RT_DENOISE_SQUARINGS_NONE = 0xFFFFFFFF
 RT_METRICS_F64, RT_METRICS_U8 = 0, 1
 RT_METRICS_EPS = 1e-2
+RT_TEMPORAL_MAX_HISTORY, RT_TEMPORAL_NORMAL_MIN, RT_TEMPORAL_PLANE_TOL = 1 << 20, 0.9, 0.02
+RT_TEMPORAL_NO_WINDOW = 0x1
 RT_TILE = 16
 ERRORS = {0: "OK", -1: "INVALID", -2: "DEVICE", -3: "NOMEM", -4: "PARSE", -5: "IO", -6: "UNSUPPORTED"}
 (RT_OK, RT_ERR_INVALID, RT_ERR_DEVICE, RT_ERR_NOMEM, RT_ERR_PARSE, RT_ERR_IO,
@@ -127,6 +129,12 @@ class rt_metrics_params(C.Structure):
                 ("peak", C.c_double), ("eps", C.c_double), ("window", C.c_double * 11)]
 
 
+class rt_temporal_params(C.Structure):
+    """Zeroed max_history, normal_min and plane_tol take the header's defaults (RT_TEMPORAL_*)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32), ("max_history", C.c_uint32),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32), ("normal_min", C.c_double), ("plane_tol", C.c_double)]
+
+
 class rt_adaptive_layout(C.Structure):
     """Byte offsets of the adaptive workspace's sub-buffers (rt_adaptive_workspace_bytes)."""
     _fields_ = [(k, C.c_uint64) for k in ("n_tiles", "acc_sum", "acc_sq", "tile_count", "tile_err", "tile_flag",
@@ -196,6 +204,9 @@ EXPORTS = {
     "rt_image_metrics_workspace_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "rt_image_metrics_async": (C.c_int, [C.POINTER(rt_metrics_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rt_temporal_history_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "rt_temporal_accumulate_async": (C.c_int, [C.POINTER(rt_temporal_params), C.POINTER(rt_render_params)] +
+                                     [C.c_void_p] * 11),
     "rt_tiles_per_rank": (C.c_int, [C.POINTER(rt_render_params), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rt_sample_chunks": (C.c_int, [C.POINTER(rt_render_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_render_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(rt_render_params), C.c_uint32, C.c_uint32,
@@ -674,6 +685,37 @@ class Scene:
             denoise_counts_async(p, d_mean.data_ptr(), d_sq.data_ptr(), d_count.data_ptr(), *tail)
         return d_out.cpu().numpy(), d_var.cpu().numpy()
 
+    def accumulate(self, params: RenderParams, mean: np.ndarray, sq: np.ndarray, count: Optional[np.ndarray] = None,
+                   history=None, prev_params: Optional[RenderParams] = None, **kw):
+        """Temporal accumulation (rt_temporal_accumulate_async) of a frame's (mean, sq) [H, W, 3] with the
+        history of the frames before it: pixel-centre rays and their first hits in this scene as
+        denoise makes them, then the kernel.  count: None (every pixel has params.spp samples) or
+        [H, W] u32.  history, prev_params: None for the first frame of a sequence, else the history
+        the previous call returned and the RenderParams it was called with.  kw: rt_temporal_params
+        fields (max_history, flags, normal_min, plane_tol).  Returns (mean [H, W, 3], sq [H, W, 3],
+        count [H, W] u32, history); the arrays go straight into denoise(..., count=count), and
+        history, a device torch.uint8 tensor, into the next call.  Runs on torch's current device,
+        where the scene must live (see denoise)."""
+        import torch
+        h, w = params.height, params.width
+        dev = dict(dtype=torch.float64, device="cuda")
+        d_mean, d_sq = (torch.from_numpy(np.ascontiguousarray(a, np.float64).reshape(h, w, 3)).cuda() for a in (mean, sq))
+        d_count = None
+        if count is not None:
+            d_count = torch.from_numpy(np.ascontiguousarray(count, np.uint32).reshape(h, w).view(np.int32)).cuda()
+        d_rays, d_hits = torch.empty((h * w, 6), **dev), torch.empty((h * w, 8), **dev)
+        d_om, d_os = torch.empty((h, w, 3), **dev), torch.empty((h, w, 3), **dev)
+        d_oc = torch.empty((h, w), dtype=torch.int32, device="cuda")
+        d_next = torch.empty(temporal_history_bytes(w, h), dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        camera_rays_async(params, d_rays.data_ptr(), stream)
+        self.intersect_async(d_rays.data_ptr(), h * w, d_hits.data_ptr(), stream_ptr=stream)
+        temporal_accumulate_async(rt_temporal_params(width=w, height=h, spp=params.spp, **kw), prev_params,
+                                  d_mean.data_ptr(), d_sq.data_ptr(), 0 if d_count is None else d_count.data_ptr(),
+                                  d_rays.data_ptr(), d_hits.data_ptr(), 0 if history is None else history.data_ptr(),
+                                  d_next.data_ptr(), d_om.data_ptr(), d_os.data_ptr(), d_oc.data_ptr(), stream)
+        return d_om.cpu().numpy(), d_os.cpu().numpy(), d_oc.cpu().numpy().view(np.uint32), d_next
+
     # ---- multi-GPU tile partition (DESIGN.md §5) ----
     def tiles_per_rank(self, params: RenderParams, world: int) -> int:
         n = C.c_uint32()
@@ -837,6 +879,25 @@ def denoise_counts_async(p: rt_denoise_params, d_mean_ptr: int, d_sq_ptr: int, d
                                          C.c_void_p(d_count_ptr), C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
                                          C.c_void_p(d_out_ptr), C.c_void_p(d_out_var_ptr), C.c_void_p(d_workspace_ptr),
                                          workspace_bytes, C.c_void_p(stream_ptr)))
+
+
+def temporal_history_bytes(width: int, height: int) -> int:
+    n = C.c_uint64()
+    _check(lib().rt_temporal_history_bytes(width, height, C.byref(n)))
+    return n.value
+
+
+def temporal_accumulate_async(p: rt_temporal_params, prev_params: Optional[RenderParams], d_mean_ptr: int, d_sq_ptr: int,
+                              d_count_ptr: int, d_rays_ptr: int, d_hits_ptr: int, d_hist_prev_ptr: int,
+                              d_hist_next_ptr: int, d_out_mean_ptr: int, d_out_sq_ptr: int, d_out_count_ptr: int,
+                              stream_ptr: int = 0):
+    """Device buffers in, device buffers out: the frame's (mean, sq [, count]) merged with the history
+    reprojected from prev_params' camera (rt_temporal_accumulate_async).  d_count_ptr 0: p.spp for
+    every pixel; prev_params None and d_hist_prev_ptr 0: the first frame of a sequence."""
+    prev = None if prev_params is None else C.byref(prev_params.to_c())
+    _check(lib().rt_temporal_accumulate_async(C.byref(p), prev, *(C.c_void_p(v) for v in (
+        d_mean_ptr, d_sq_ptr, d_count_ptr, d_rays_ptr, d_hits_ptr, d_hist_prev_ptr, d_hist_next_ptr, d_out_mean_ptr,
+        d_out_sq_ptr, d_out_count_ptr, stream_ptr))))
 
 
 def ssim_window(sigma: float = 1.5) -> np.ndarray:

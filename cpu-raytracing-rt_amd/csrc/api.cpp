@@ -1102,6 +1102,92 @@ int rt_image_metrics_async(const rt_metrics_params* p, const void* d_a, const vo
     return RT_OK;
 }
 
+static int temporal_size(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0) return set_error(RT_ERR_INVALID, "width/height must be > 0");
+    if (width > 65535 || height > 65535) return set_error(RT_ERR_INVALID, "width/height must be <= 65535");
+    return RT_OK;
+}
+
+int rt_temporal_history_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
+    if (!bytes) return set_error(RT_ERR_INVALID, "bytes is NULL");
+    if (int rc = temporal_size(width, height)) return rc;
+    const uint64_t n = (uint64_t)width * height;
+    *bytes = temporal_guide_bytes(n) + temporal_colour_bytes(n);
+    return RT_OK;
+}
+
+int rt_temporal_accumulate_async(const rt_temporal_params* p, const rt_render_params* prev, const double* d_mean,
+                                 const double* d_sq, const uint32_t* d_count, const double* d_rays, const rt_hit* d_hits,
+                                 const void* d_hist_prev, void* d_hist_next, double* d_out_mean, double* d_out_sq,
+                                 uint32_t* d_out_count, void* stream) {
+    if (!p) return set_error(RT_ERR_INVALID, "params is NULL");
+    if (int rc = temporal_size(p->width, p->height)) return rc;
+    if ((prev != nullptr) != (d_hist_prev != nullptr))
+        return set_error(RT_ERR_INVALID, "prev_camera and hist_prev go together: both or neither");
+    TemporalSettings S;
+    std::memset(&S, 0, sizeof(S));
+    S.width = p->width; S.height = p->height; S.spp = p->spp; S.flags = p->flags;
+    if (!d_count && (p->spp < 1 || p->spp > (1u << 30))) return set_error(RT_ERR_INVALID, "spp must be 1..2^30");
+    if (p->max_history > (1u << 30)) return set_error(RT_ERR_INVALID, "max_history must be <= 2^30 (0: the default)");
+    S.max_history = p->max_history ? p->max_history : RT_TEMPORAL_MAX_HISTORY;
+    if (p->flags & ~RT_TEMPORAL_NO_WINDOW) return set_error(RT_ERR_INVALID, "unknown flag");
+    if (!(p->normal_min >= 0.0) || !(p->normal_min <= 1.0))
+        return set_error(RT_ERR_INVALID, "normal_min must be in (0, 1] (0: the default)");
+    if (!(p->plane_tol >= 0.0) || !std::isfinite(p->plane_tol))
+        return set_error(RT_ERR_INVALID, "plane_tol must be finite and > 0 (0: the default)");
+    S.normal_min = p->normal_min == 0.0 ? RT_TEMPORAL_NORMAL_MIN : p->normal_min;
+    S.plane_tol = p->plane_tol == 0.0 ? RT_TEMPORAL_PLANE_TOL : p->plane_tol;
+    if (prev) {
+        if (prev->width != p->width || prev->height != p->height)
+            return set_error(RT_ERR_INVALID, "prev_camera's width/height differ from the frame's");
+        if (prev->fov_axis != RT_FOV_X && prev->fov_axis != RT_FOV_Y) return set_error(RT_ERR_INVALID, "bad fov_axis");
+        rt_render_params cam = *prev;
+        cam.spp = 1;  // not read here; make_kparams' chunking wants one
+        const KParams k = make_kparams(&cam, 0, 1);
+        S.has_prev = 1;
+        S.fw = k.fw; S.fh = k.fh; S.tan_x = k.tan_x; S.tan_y = k.tan_y;
+        // the dual basis: the reference normalises right, up and forward each alone (scene.rs:169-175),
+        // so they need not be orthogonal and plain dot products with them are not the inverse
+        const V3 r = load3(prev->cam_right), u = load3(prev->cam_up), f = load3(prev->cam_forward);
+        const V3 uf = cross(u, f);
+        const double det = dot(r, uf);
+        if (det == 0.0 || !std::isfinite(det))
+            return set_error(RT_ERR_INVALID, "prev_camera's basis is singular or not finite");
+        const V3 rs = uf / det, us = cross(f, r) / det, fs = cross(r, u) / det;
+        const V3 pos = load3(prev->cam_position);
+        const V3 rows[4] = {pos, rs, us, fs};
+        double* dst[4] = {S.pos, S.rs, S.us, S.fs};
+        for (int i = 0; i < 4; ++i) {
+            dst[i][0] = rows[i].x; dst[i][1] = rows[i].y; dst[i][2] = rows[i].z;
+        }
+    }
+    if (!d_mean || !d_sq || !d_rays || !d_hits || !d_hist_next || !d_out_mean || !d_out_sq || !d_out_count)
+        return set_error(RT_ERR_INVALID, "mean/sq/rays/hits/hist_next/out_mean/out_sq/out_count is NULL");
+    if (((uintptr_t)d_mean | (uintptr_t)d_sq | (uintptr_t)d_rays | (uintptr_t)d_hits | (uintptr_t)d_out_mean |
+         (uintptr_t)d_out_sq) & 15u)
+        return set_error(RT_ERR_INVALID, "the f64 buffers and the hits must be 16-byte aligned");
+    if (((uintptr_t)d_hist_prev | (uintptr_t)d_hist_next) & 255u)
+        return set_error(RT_ERR_INVALID, "the history blocks must be 256-byte aligned");
+    if (((uintptr_t)d_count | (uintptr_t)d_out_count) & 3u)
+        return set_error(RT_ERR_INVALID, "the counts must be 4-byte aligned");
+    const uint64_t n = (uint64_t)p->width * p->height, hist = temporal_guide_bytes(n) + temporal_colour_bytes(n);
+    // an output may overlap neither what the kernel reads nor another output
+    struct Range { const void* p; uint64_t bytes; };
+    const Range outs[4] = {{d_hist_next, hist}, {d_out_mean, n * 24}, {d_out_sq, n * 24}, {d_out_count, n * 4}};
+    const Range ins[6] = {{d_mean, n * 24}, {d_sq, n * 24}, {d_count, d_count ? n * 4 : 0}, {d_rays, n * 48},
+                          {d_hits, n * 64}, {d_hist_prev, d_hist_prev ? hist : 0}};
+    for (int o = 0; o < 4; ++o)
+        for (int i = 0; i < 6 + 3 - o; ++i) {  // the inputs, then the outputs after this one
+            const Range& in = i < 6 ? ins[i] : outs[o + 1 + (i - 6)];
+            const uintptr_t a = (uintptr_t)outs[o].p, b = (uintptr_t)in.p;
+            if (in.bytes && a < b + in.bytes && b < a + outs[o].bytes)
+                return set_error(RT_ERR_INVALID, "hist_next/out_mean/out_sq/out_count overlaps an input, hist_prev or another output");
+        }
+    HIP_TRY(launch_temporal(S, d_mean, d_sq, d_count, d_rays, d_hits, d_hist_prev, d_hist_next, d_out_mean, d_out_sq,
+                            d_out_count, (hipStream_t)stream));
+    return RT_OK;
+}
+
 int rt_read_stats(rt_scene* s, rt_stats* out, int reset) {
     if (!s || !out) return set_error(RT_ERR_INVALID, "scene/out is NULL");
     DEVICE_GUARD(s);

@@ -242,6 +242,21 @@ struct MetricsSettings {
 uint64_t metrics_blocks(uint32_t width, uint32_t height);
 hipError_t launch_image_metrics(const MetricsSettings& S, const void* a, const void* b, double* rel, double* ssim,
                                 double* summary, double* part, hipStream_t st);
+// temporal.hip: temporal accumulation (rt_temporal_accumulate_async) with rt_temporal_params' defaults
+// resolved and the previous camera as the kernel takes it: make_kparams' tan_x, tan_y, fw, fh and the
+// dual basis (rs, us, fs) of (right, up, forward).  has_prev 0: no history, the camera is not read.
+// A history block is temporal_guide_bytes(W * H) of guide records, then temporal_colour_bytes(W * H).
+struct TemporalSettings {
+    uint32_t width, height, spp, max_history, flags, has_prev;
+    double normal_min, plane_tol;
+    double fw, fh, tan_x, tan_y;
+    double pos[3], rs[3], us[3], fs[3];
+};
+uint64_t temporal_guide_bytes(uint64_t n_pixels);
+uint64_t temporal_colour_bytes(uint64_t n_pixels);
+hipError_t launch_temporal(const TemporalSettings& S, const double* mean, const double* sq, const uint32_t* count,
+                           const double* rays, const rt_hit* hits, const void* hist_prev, void* hist_next,
+                           double* out_mean, double* out_sq, uint32_t* out_count, hipStream_t st);
 // ellipsoid records: aux = dev_rcp(radii), the device's own reciprocals (rt_device.h)
 hipError_t launch_ell_rcp(DevShape* shapes, uint32_t n, hipStream_t st);
 // checksum_kernel: order-free content hash of a device array (rt_scene_checksum)

@@ -590,6 +590,81 @@ int rt_image_metrics_async(const rt_metrics_params* p, const void* d_a, const vo
                            double* d_rel /* NULL ok */, double* d_ssim /* NULL ok */, double* d_summary,
                            void* d_workspace, uint64_t workspace_bytes, void* hip_stream);
 
+/* ---- temporal accumulation: frame history reprojected through a camera change (no counterpart in the reference) ----
+   The temporal half of SVGF; the denoiser above is the spatial half.  The scene is static and only the
+   camera moves: what pixel p of the current frame sees is looked up where the previous camera saw it, and
+   the previous frame's (mean, second moment, count) there are merged with p's own, so a surface both
+   frames see keeps its samples.  Rational arithmetic (+ - * /, floor, comparisons) in a fixed order, IEEE,
+   nothing fused: the outputs are the bits of a float64 restatement on the host
+   (tests/test_gpu_temporal.py).  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z throughout.
+   Current frame, per pixel p: n_c = min(d_count ? d_count[p] : spp, 2^30); cur_ok = n_c >= 1 and the
+   six values mean_c, sq_c all finite.  Guide, the denoiser's: hit_p = (prim != RT_HIT_MISS), n_p =
+   shading_normal, t_p, x_p = origin + t * dir (unfused); n_p, t_p and x_p are rounded to f32 and widened
+   back where they are compared with history (the tap tests) and where they are stored.
+   Previous camera, on the host: tan_x, tan_y, fw = W, fh = H as the renderer makes them (tan(fov / 2) on
+   the fov axis, the other divided by the aspect), and the dual basis of (right, up, forward), which need
+   not be orthogonal (the reference normalises each vector alone): with cross(a, b) = (a.y*b.z - a.z*b.y,
+   a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), det = dot(right, cross(up, forward)), r* = cross(up, forward) /
+   det, u* = cross(forward, right) / det, f* = cross(right, up) / det, each component divided.  det zero
+   or not finite: RT_ERR_INVALID.
+   Reprojection, f64, from the unrounded x_p: v = x_p - prev_position; zc = dot(v, f*), xc = dot(v, r*),
+   yc = dot(v, u*); gx = ((xc / zc) / tan_x + 1) * 0.5 * fw - 0.5; gy = ((-(yc / zc)) / tan_y + 1) * 0.5 *
+   fh - 0.5, evaluated left to right.  p has a candidate when hit_p, zc > 0, -1 <= gx < W and -1 <= gy < H
+   (each comparison false for a NaN).  x0 = floor(gx), y0 = floor(gy), ax = gx - x0, ay = gy - y0.
+   Taps q = (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner, weight b = (i ? ax : 1 - ax) * (j ? ay :
+   1 - ay).  A tap is valid when it lies inside the image, its history record has count >= 1 and the hit
+   flag, dot(n_p, n_q) >= normal_min, and |dot(n_p, x_q - x_p)| <= plane_tol * t_p.  Over the valid taps,
+   in tap order: sw = sw + b, sm_c = sm_c + b * mean_q,c, ss_c = ss_c + b * sq_q,c, n_min = min(count_q).
+   hist_ok = sw > 0; then h_c = sm_c / sw, hs_c = ss_c / sw, n_h = min(n_min, max_history).
+   Merge:  cur_ok and hist_ok: N = n_h + n_c, out_c = ((double)n_h * h_c + (double)n_c * mean_c) /
+             (double)N, sq likewise with hs_c, out_count = N;
+           only cur_ok: the current values, out_count = n_c;
+           only hist_ok: h_c and hs_c (a hole is filled), out_count = n_h;
+           neither: the current values as they are (a NaN passes through), out_count = 0.
+   New history record of p: the colour is the six outputs; count = out_count, but 0 when any of the six
+   is not finite; the guide of p, the hit flag clear for a miss.  Without d_hist_prev every pixel is the
+   "no history" case: that is how a sequence starts.
+   History: a caller-owned block of rt_temporal_history_bytes bytes, 80 B a pixel in two arrays, each
+   rounded up to 256 B: [H][W] guide records of 32 B, {nx, ny, nz, px, py, pz} f32, count u32, flags u32
+   (bit 0: hit), then [H][W] colour records of 48 B, mean r, g, b and sq r, g, b as f64.  A call reads
+   d_hist_prev and writes d_hist_next; the caller ping-pongs two blocks (taps read arbitrary pixels, so
+   the accumulation cannot run in place). */
+#define RT_TEMPORAL_MAX_HISTORY (1u << 20)
+#define RT_TEMPORAL_NORMAL_MIN  0.9
+#define RT_TEMPORAL_PLANE_TOL   0.02
+/* every tap straight from global memory: the same bits, without the kernel's LDS window of the history
+   (for tests and measurements) */
+#define RT_TEMPORAL_NO_WINDOW   0x1u
+typedef struct rt_temporal_params {
+    uint32_t width, height;
+    uint32_t spp;          /* the current frame's samples when d_count is NULL; 1..2^30   */
+    uint32_t max_history;  /* cap, in samples, on what history contributes; 0 = default; <= 2^30 */
+    uint32_t flags, _pad;
+    double normal_min;     /* 0 = default; else finite, in (0, 1]                         */
+    double plane_tol;      /* 0 = default; else finite, > 0                                */
+} rt_temporal_params;
+/* Bytes of one history block.  Zero width or height, or one above 65535: RT_ERR_INVALID. */
+int rt_temporal_history_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+/* The accumulation above on the current device, stream-ordered, in caller-owned memory: no scene handle
+   and no hidden allocation, so two calls on different streams share nothing.  d_mean, d_sq [H][W][3] f64
+   (rt_render_moments, rt_adaptive_resolve_async, or unpacked tiles); d_count NULL or [H][W] u32; d_rays
+   [H*W][6] f64 and d_hits [H*W], the current frame's pixel-centre rays and their first hits, as the
+   denoiser takes them; prev_camera the camera of the frame that wrote d_hist_prev (its cam_*, fov and
+   fov_axis are read; its width and height must be p's).  d_out_mean, d_out_sq [H][W][3] f64 and
+   d_out_count [H][W] u32 are what rt_denoise_counts_async and rt_error_estimate_counts_async take.
+   RT_ERR_INVALID, all checked before any device call: zero width or height (or above 65535), prev_camera
+   without d_hist_prev or the reverse, a prev_camera of another size or with a bad fov_axis, a previous
+   basis that is singular or not finite, spp (when d_count is NULL), max_history, flags, normal_min or
+   plane_tol out of range, a NULL required pointer, misalignment (f64 buffers and hits 16 bytes, the
+   history blocks 256, counts 4), an output or d_hist_next overlapping an input, d_hist_prev or another
+   output. */
+int rt_temporal_accumulate_async(const rt_temporal_params* p,
+        const rt_render_params* prev_camera,        /* NULL iff d_hist_prev is NULL */
+        const double* d_mean, const double* d_sq, const uint32_t* d_count /* NULL ok */,
+        const double* d_rays, const rt_hit* d_hits,
+        const void* d_hist_prev /* NULL: first frame */, void* d_hist_next,
+        double* d_out_mean, double* d_out_sq, uint32_t* d_out_count, void* hip_stream);
+
 /* Diagnostics: the scene's raw device counter words (n <= 64), accumulated by
    RT_FLAG_STATS renders: words 0..9 are rt_stats' counters; word 10 counts the
    last-bounce light queries the timed (no-stats) kernel skips because they cannot

@@ -2,6 +2,9 @@
 built librt_amd.so (reads the gfx950 code object's AMDGPU metadata notes).
 
     python tools/kernel_regs.py [path/to/librt_amd.so] [name-filter]
+
+The filter is a substring of the demangled name: "_kernel" (the default) for the path and trace
+kernels, "dn_" for the denoiser's, "tp_" for temporal.hip's tp_accumulate, "" for every kernel.
 """
 import os
 import re
